@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CREMA-D DGL train step on N MI355X (one process per GPU, RCCL over xGMI).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python bench.py --gpus N --steps K --warmup W        (starts the launcher below as a child process itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,7 +11,9 @@ synthetic CREMA-D-shaped batch that is already resident in HBM: both ResNet18 en
 the gradient-truncated fusion head + three cross-entropies, both encoder backwards, the
 per-bucket gradient all-reduce (N > 1), global-norm clipping, the logged per-encoder gradient
 statistics and the SGD(momentum, weight decay) update -- nothing skipped, nothing cached.
-Rank 0 prints ONE JSON line (see the driver contract); `roofline` is measured live with HIP
+Rank 0 prints ONE JSON line (see the driver contract).  A plain run sets up, warms up, times the
+K steps, writes the last step's outputs if --dump-outputs is given and prints that line; every other
+figure below is measured only with --full.  `roofline` is measured live with HIP
 events around every launch of the dominant kernel inside the timed region; `cpu_baseline` times the
 PyTorch-CPU-operator restatement of the step (oracle/torch_step.py; the plain-C port of oracle/ rides
 along as `c_port`) on this machine's host cores; `comparators.torch_rocm` times that same restatement
@@ -89,6 +91,11 @@ def parse():
     ap.add_argument("--no-comparator", action="store_true", help="skip comparators.torch_rocm (stock PyTorch-ROCm step)")
     ap.add_argument("--comparator-find", action="store_true",
                     help="comparators.torch_rocm in MIOpen find mode, all variants (minutes of warm-up; profiles/ keeps one such run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel table and roofline tap, clip statistics, "
+                         "f32_exact, extra_workloads, comparators, cpu_baseline and (N > 1) comm; the --no-* flags above thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -220,6 +227,32 @@ def build_model(wl, batch, dev):
     model.to(dev)
     model.train()
     return model, args
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of each flat arena by --dump-outputs (3 x 8 MB; the arenas hold 22 M+ each)
+
+
+def dump_outputs(tr, res, out_dir):
+    """What the last step handed its caller, as DIR/<name>.npy: the three logit sets, the losses and gradient statistics of
+    DGLTrainer.read(), the BatchNorm running statistics, and a fixed seeded sample (same positions in every run of the same
+    model) of the updated parameters, their gradients and the momentum."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = tr.params.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(tr.params.device)
+    m = tr.model
+    bn = [b.reshape(-1) for net in (m.audio_net, m.visual_net) for name, b in net.named_buffers()
+          if name.endswith(("running_mean", "running_var"))]
+    arrays = {"out": res["out"], "out_a": res["out_a"], "out_v": res["out_v"],
+              "losses": [res["loss_f"], res["loss_a"], res["loss_v"]],
+              "grad_stats": [res["total_norm"], res["clip_coef"], res["audio_grad_sum"], res["visual_grad_sum"]],
+              "grad_norm": list(res["grad_norm"].values()), "grad_absmean": list(res["grad_absmean"].values()),
+              "bn_running_stats": torch.cat(bn).float().cpu().numpy() if bn else [],
+              "params_sample": tr.params[idx].cpu().numpy(), "grads_sample": tr.grads[idx].cpu().numpy(),
+              "momentum_sample": tr.momentum[idx].cpu().numpy()}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        np.save(os.path.join(out_dir, name + ".npy"), v if v.dtype in (np.float32, np.float64) else v.astype(np.float64))
 
 
 def extra_leg(name, a, dev, lib, collect, steps=30, warmup=15):
@@ -356,7 +389,8 @@ def main():
     counter = [0]
     # (total norm, clip coefficient) of every step of the timed region, copied device-to-device behind each step (8 bytes on
     # the step's own stream: a measuring tap like the HIP events, read once after the region) -> clip_active_steps
-    tr.stats_log = torch.zeros((a.steps, 2), device=dev)
+    if a.full:
+        tr.stats_log = torch.zeros((a.steps, 2), device=dev)
 
     def step():
         spec, image, label = data[counter[0] % len(data)]
@@ -408,9 +442,9 @@ def main():
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize()
-    prof = (not a.no_prof) and rank == 0
+    prof = a.full and not a.no_prof and rank == 0
     kernels, dominant = None, None
-    if not a.no_prof:
+    if a.full and not a.no_prof:
         # untimed calibration: every launch tapped (costs ~10 % throughput), gives the per-kernel table and
         # names the dominant kernel; the timed region then taps ONLY that kernel's launches.  Every rank runs
         # the three steps (they contain the gradient all-reduces); only rank 0 taps.
@@ -445,7 +479,7 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
     tr.stats_log_pos = None
-    clip_log = tr.stats_log.cpu().numpy()
+    clip_log = tr.stats_log.cpu().numpy() if tr.stats_log is not None else None
     if world > 1:
         import torch.distributed as dist
 
@@ -453,6 +487,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     res = tr.read()
+    if a.dump_outputs and rank == 0:  # (before anything below runs more steps or overwrites the arenas)
+        dump_outputs(tr, res, a.dump_outputs)
     roof = None
     if prof:
         lib.gdl_prof_enable(0)
@@ -530,7 +566,7 @@ def main():
                 acc.setdefault(n0 + "->" + n1, []).append(e0.elapsed_time(e1))
         phases = {k: round(sum(v) / len(v), 3) for k, v in acc.items()}
     comm = None
-    if world > 1:
+    if a.full and world > 1:
         # What the collectives cost and how much of it the backward hides: each bucket's all-reduce alone, and the
         # step with the reducer moving no data (same kernels, same events; NOT a valid training step -- timing only).
         import torch.distributed as dist
@@ -603,7 +639,7 @@ def main():
             comm["schedule_variants_ms"] = variants
             comm["default_schedule"] = (f"visual_wgrad_{vis0}__early_backward_{'on' if early0 is not False else 'off'}"
                                         f"__audio_lane_{'on' if lane0 else 'off'}")
-    if rank == 0:
+    if a.full and rank == 0:
         # the headline measurement is complete here: leave it on stderr (and in gpurun_out/ when that exists) BEFORE the secondary
         # legs below -- a hard fault in one of them (graph capture, MIOpen, an OOM kill) must not take it along
         head = {"metric": wl["metric"], "value": round(world * B * a.steps / elapsed, 2), "unit": "samples/s", "n_gpus": world,
@@ -618,7 +654,7 @@ def main():
         except OSError:
             pass
     f32_exact = None
-    if a.dtype == "bf16" and not a.no_f32:
+    if a.full and a.dtype == "bf16" and not a.no_f32:
         # the exact-parity mode (f32 storage, f32-input MFMA == an fmaf chain) on the same workload: a short run
         del tr
         torch.cuda.empty_cache()
@@ -646,7 +682,7 @@ def main():
         del tr32
     extra = None
     comparators = None
-    if world == 1 and pg is None:
+    if a.full and world == 1 and pg is None:
         try:
             del tr
         except NameError:
@@ -679,6 +715,8 @@ def main():
     if rank != 0:
         return
     value = world * B * a.steps / elapsed
+    clip = None if clip_log is None else (int((clip_log[:, 1] < 1.0).sum()), [round(float(clip_log[:, 0].min()), 4),
+                                                                                round(float(clip_log[:, 0].max()), 4)])
     out = {
         "metric": wl["metric"],
         "value": round(value, 2), "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -689,8 +727,8 @@ def main():
                    "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
                    # which regime of clip_grad_norm_(40) the timed steps ran in (the kernels are the same; an inactive clip
                    # skips the 4 n-byte write-back of the scaled gradients in sgd_kernel)
-                   "clip_regime": f"clip active in {int((clip_log[:, 1] < 1.0).sum())} of {a.steps} timed steps "
-                                  f"({len(data)} distinct batches cycled, {a.warmup} warm-up steps)",
+                   "clip_regime": f"clip active in {clip[0]} of {a.steps} timed steps "
+                                  f"({len(data)} distinct batches cycled, {a.warmup} warm-up steps)" if clip else None,
                    "buckets": "fusion head | audio layer4 | audio rest | visual layer4 | visual rest, RCCL all-reduce, layer4 "
                               "buckets overlapped with the rest of the backward" if world > 1 else "none"},
         "samples_per_sec_per_gpu": round(value / world, 2),
@@ -701,12 +739,11 @@ def main():
         "clip_coef": round(res["clip_coef"], 4),
         # steps of the timed region in which clip_grad_norm_ actually scaled the gradients (coefficient < 1; the kernels do
         # the same work either way) and the range the global norm moved in
-        "clip_active_steps": int((clip_log[:, 1] < 1.0).sum()), "total_norm_range": [round(float(clip_log[:, 0].min()), 4),
-                                                                                    round(float(clip_log[:, 0].max()), 4)],
+        "clip_active_steps": clip[0] if clip else None, "total_norm_range": clip[1] if clip else None,
         "roofline": roof, "kernels": kernels, "phases_ms": phases, "f32_exact": f32_exact, "comm": comm,
         "batches": len(data), "src_hash": src_hash(), "extra_workloads": extra, "comparators": comparators,
     }
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_batch, a.cpu_torch_batch, a.cpu_threads, wl)
     else:
         out["cpu_baseline"] = None

@@ -1133,3 +1133,42 @@ def test_alternate_paths_pass_the_goldens(knobs):
                         "encoder_golden or step_golden", "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert " passed" in r.stdout and "no tests ran" not in r.stdout
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the plain run times exactly K steps, leaves every figure
+    of --full out of its line, and writes what the last timed step returned as float32 / float64 .npy files (64 MB at most).
+    Two runs with the same arguments start from the same seeded model and batches, so their outputs agree (different inputs
+    would differ at O(1); the bound leaves room for reordered sums)."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "4", "--batches", "2", "--dump-outputs", str(d)], cwd=root, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in files})
+    line, got = lines[0], dumps[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "samples/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["ms_per_step"] > 0
+    assert abs(line["ms_per_step"] * 3 / 1e3 - line["timed_region_s"]) <= 1e-4  # (timed_region_s carries 4 decimals)
+    for k in ("roofline", "kernels", "clip_active_steps", "f32_exact", "comm", "extra_workloads", "comparators", "cpu_baseline"):
+        assert line[k] is None, k
+    assert set(got) == {"out", "out_a", "out_v", "losses", "grad_stats", "grad_norm", "grad_absmean", "bn_running_stats",
+                        "params_sample", "grads_sample", "momentum_sample"}
+    assert all(v.dtype in (np.float32, np.float64) and v.size > 0 for v in got.values())
+    assert got["out"].shape == got["out_a"].shape == got["out_v"].shape == (4, 6)
+    np.testing.assert_allclose(got["losses"], [line["loss_f"], line["loss_a"], line["loss_v"]], atol=1e-5)
+    assert got["params_sample"].shape == (1 << 21,) and np.isfinite(got["params_sample"]).all()
+    for k, v in got.items():
+        w = dumps[1][k]
+        assert w.shape == v.shape and np.abs(w - v).max() <= 1e-2 * max(float(np.abs(v).max()), 1e-6), k
