@@ -1026,12 +1026,11 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pers_kernel(ConvArgs a, int 
 // fragments (wb + 2048*n), all through instruction offsets
 template <int MI, int NI>
 __device__ __forceinline__ void slab_reads(uint4 (&px)[MI], uint4 (&wf)[NI], const unsigned (&pb)[MI], unsigned wb) {
-    static_assert(MI >= 2 && MI <= 4, "MI");
+    static_assert(MI == 2 || MI == 3, "MI");
     static_assert(NI == 4 || NI == 8, "NI");
     px[0] = lds_read16_asm_off<0>(pb[0]);
     px[1] = lds_read16_asm_off<2048>(pb[1]);
-    if constexpr (MI >= 3) px[2] = lds_read16_asm_off<4096>(pb[2]);
-    if constexpr (MI == 4) px[3] = lds_read16_asm_off<6144>(pb[3]);
+    if constexpr (MI == 3) px[2] = lds_read16_asm_off<4096>(pb[2]);
     wf[0] = lds_read16_asm_off<0>(wb);
     wf[1] = lds_read16_asm_off<2048>(wb);
     wf[2] = lds_read16_asm_off<4096>(wb);
@@ -1168,7 +1167,7 @@ __global__ __launch_bounds__(NWV * 64, (NWV == 8) ? 2 : ((BM >= 192 && BN == 128
             if (nslab == 1 && tap == 0 && kc > kc0) {
                 // single slab buffer: every wave is past its last read of the previous chunk's slab (barrier above);
                 // fetch this chunk's slab now -- the wait is exposed once per chunk (9 K-steps), the other block of
-                // the CU works meanwhile, and the LDS it saves is what lets two 256-row blocks share a CU
+                // the CU works meanwhile, and the LDS it saves is what lets two 192-row blocks share a CU
                 load_slab(0, kc);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -1205,7 +1204,7 @@ __global__ __launch_bounds__(NWV * 64, (NWV == 8) ? 2 : ((BM >= 192 && BN == 128
                 asm volatile("" ::: "memory");
             };
             if constexpr ((MI + NI) * 8 > 80) {
-                // big tile (MI = 4, NI = 8): 128 accumulator registers leave room for ONE half's fragments (48) if two
+                // big tile (MI = 3, NI = 8): 96 accumulator registers leave room for ONE half's fragments (44) if two
                 // waves are to share a SIMD: the halves are read one after the other
                 uint4 px[MI], wf[NI];
                 slab_reads<MI, NI>(px, wf, pb, wb0);
@@ -1795,23 +1794,7 @@ struct TileCfg {
     int bm, bn;
 };
 
-static int forced_cfg() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = tune_env("GDL_CONV_CFG");  // tuning aid: 1 = 256x64, 3 = 64x64, 4 = 128x64
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
-static TileCfg pick_cfg(int M, int OC, int dtype) {
-    (void)dtype;
-    switch (forced_cfg()) {
-        case 1: return {256, 64};
-        case 3: return {64, 64};
-        case 4: return {128, 64};
-        default: break;
-    }
+static TileCfg pick_cfg(int M, int OC) {
     // Measured on MI355X (tools/bench_conv.py, CREMA-D B=64 shapes): 256x64 wins whenever it still
     // yields >= ~160 blocks, also for wide layers (the A panel re-read per N-tile is served by L2);
     // below that the smaller M-tiles fill the chip better.
@@ -1824,244 +1807,53 @@ static TileCfg pick_cfg(int M, int OC, int dtype) {
     return {64, 64};
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int MODE>
-static int launch_one(ConvArgs& a, hipStream_t st) {
-    using SM = ConvSmem<BM, BN, T>;
-    a.mtiles = ceil_div(a.M, BM);
-    auto kfn = conv_igemm_kernel<T, BM, BN, WM, WN, MODE>;
-    static DevOnce attr_set;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, SM::BYTES);
-        if (e != hipSuccess) return check_hip(e, "hipFuncSetAttribute(conv_igemm)");
-        attr_set = true;
-    }
-    const int ntn = a.OC / BN;
-    const int grid = xcd_grid(a.mtiles * ntn);
-    static char pname[96] = "";
-    if (!pname[0])
-        snprintf(pname, sizeof(pname), "gdl::conv_igemm_kernel<%s, %d, %d, %d, %d, %d>", prof_tname<T>(), BM, BN, WM, WN, MODE);
-    ProfScope prof(pname, PROF_MFMA, st, a.flops, true, a.hbm_bytes);
-    hipExtLaunchKernelGGL(kfn, dim3(grid), dim3(256), SM::BYTES, st, prof.e0(), prof.e1(), 0, a);
-    GDL_CHECK_LAUNCH("conv_igemm_kernel");
-    return GDL_OK;
-}
-
-template <typename T, int BM, int BN, int MODE, int NWV = 4>
-static int launch_slab(ConvArgs& a, size_t lds, hipStream_t st) {
-    a.mtiles = ceil_div(a.M, BM);
-    auto kfn = conv3x3_slab_kernel<T, BM, BN, MODE, NWV>;
-    static DevOnce attr_set;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return check_hip(e, "hipFuncSetAttribute(conv3x3_slab)");
-        attr_set = true;
-    }
-    const int grid = xcd_grid(a.mtiles * (a.OC / BN) * (a.ksplit > 1 ? a.ksplit : 1));
-    static char pname[96] = "";
-    if (!pname[0])
-        snprintf(pname, sizeof(pname), "gdl::conv3x3_slab_kernel<%s, %d, %d, %d, %d>", prof_tname<T>(), BM, BN, MODE, NWV);
-    ProfScope prof(pname, PROF_MFMA, st, a.flops, true, a.hbm_bytes);
-    hipExtLaunchKernelGGL(kfn, dim3(grid), dim3(NWV * 64), lds, st, prof.e0(), prof.e1(), 0, a);
-    GDL_CHECK_LAUNCH("conv3x3_slab_kernel");
-    return GDL_OK;
-}
-
-// which kernel / tile a convolution runs with (shared by the launcher and by the BatchNorm partial count)
-struct ConvPlan {
-    int slab;  // 1: conv3x3_slab_kernel
-    int bm, bn;
-    size_t lds;
-    int single;  // slab kernel: one slab buffer
-    int c64;     // 1: conv3x3_c64_kernel (persistent; BatchNorm partial rows = C64_GRID)
-    int nwv8;    // slab kernel: the 128 x 128 tile on 512 threads (small layers: one block per CU at most)
-    int pslab;   // 1: conv3x3_pslab_kernel (persistent, pipelined; round 6) -- bm / bn / single / lds describe ITS launch
-    int grid;    // pslab: blocks of the launch = BatchNorm partial rows
+// which kernel and tile a convolution launch runs with: one plan, read by the launcher, by the BatchNorm partial-row queries
+// (conv_tiles_m ...) and by the split-K workspace query
+enum class ConvKind {
+    FLAT,   // conv_igemm_kernel: the gathered implicit GEMM
+    SLAB,   // conv3x3_slab_kernel (stride-1 3x3), four waves
+    SLAB8,  // conv3x3_slab_kernel, the 128 x 128 tile on eight waves (small layers: one block per CU at most)
+    C64,    // conv3x3_c64_kernel: 64 -> 64 channels, persistent, weights in registers
+    PSLAB,  // conv3x3_pslab_kernel: persistent, pipelined (round 6)
 };
+struct ConvPlan {
+    ConvKind kind;
+    int bm, bn;
+    int nslab;   // slab kinds: slab buffers (2: double-buffered when the K-loop has more than one channel chunk)
+    size_t lds;  // slab kinds: dynamic LDS of the launch
+    int grid;    // blocks of the launch
+    int split;   // K splits (> 1: fp32 partials in the caller's workspace, folded by splitk_finish_kernel)
+    int rows;    // BatchNorm partial rows the launch writes (a split launch: those of the unsplit one, run_conv zeroes the rest)
+};
+// what a launch carries besides its tensors and geometry (run_conv's options; the planner reads them too)
+struct ConvOpts {
+    const void* addend = nullptr;
+    float* stats = nullptr;
+    const uint8_t* relu_bits = nullptr;
+    const void* dy_ds = nullptr;  // the downsample pair folded into a stride-2 data gradient (conv_dgrad_ds)
+    const void* w_ds = nullptr;
+    const float* bias = nullptr;
+    void* gelu_out = nullptr;
+    const void* gelu_u = nullptr;
+    const BwdStats* bw = nullptr;
+    const BnAcc* sacc = nullptr;
+    const SplitWs* split = nullptr;
+};
+
 static size_t c64_lds_bytes(int W, bool single = false) {
     // slabs, zero KiB, BW: constants (512 B) + accumulator rows (2 KiB)
     const size_t b = (single ? 1 : 2) * (size_t)((C64_BM + 2 * W + 2 + 7) / 8) * 1024 + 1024 + 512 + 2048;
     return b > (size_t)72 * 1024 ? b : (size_t)72 * 1024;  // the prologue stages the 72 KiB filter through the same LDS
 }
-static bool c64_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = tune_env("GDL_C64");  // tuning aid: 0 = the slab kernel for the 64 -> 64 channel layers too
-        v = e ? atoi(e) : 1;
-    }
-    return v != 0;
-}
-static int slab_cfg() {
-    static int v = -1;
-    if (v < 0) {
-        // tuning aid, bits: 1 = allow the 256 x 128 single-slab tile, 2 = the 192 x 128 one.  Re-swept inside the step after the
-        // layer-1 / stem kernels became persistent (tools/ab_env.sh, 4 A/B rounds): 192-row tiles 5.85 ms, both 5.86, 256-row 5.91
-        const char* e = tune_env("GDL_SLAB_CFG");
-        v = e ? atoi(e) : 2;
-    }
-    return v;
-}
-// fewest blocks for which the 192 / 256 x 128 tiles are used, and for which the 128-channel tile is used at all: the small layers
+// fewest blocks for which the 192 x 128 tile is used, and for which the 128-channel tile is used at all: the small layers
 // (visual layer 4, audio layers 3 / 4) keep 64-wide tiles or the 8-wave form -- twice the blocks (knob sweeps of rounds 2-4: 100 ->
 // 384 is -0.5 % step time, the defaults stayed twice; GDL_SLAB_BIG_MIN / GDL_SLAB_BN128_MIN: tools/experiments/r5_pruned_knobs.diff.txt)
 static constexpr long slab_big_min() { return 128; }
 static constexpr long slab_bn128_min() { return 384; }
-static ConvPlan plan_conv_base(int dtype, int M, int OC, int IC, int W, int R, int S, int stride, int pad, bool allow_nwv8 = true) {
-    ConvPlan p{};
-    static int noslab = -1;
-    if (noslab < 0) {
-        const char* e = tune_env("GDL_CONV_NOSLAB");  // tuning aid
-        noslab = e ? atoi(e) : 0;
-    }
-    static int slab_bm = -1;
-    if (slab_bm < 0) {
-        const char* e = tune_env("GDL_SLAB_BM");  // tuning aid: force the slab kernel's M-tile (128 / 256)
-        slab_bm = e ? atoi(e) : 0;
-    }
-    // LDS budget of the slab kernel: 80 KB (two blocks per CU); a layer too wide for that (the 79-pixel audio layer 2 of the
-    // Kinetics-Sounds shapes) still runs better on it with one block per CU than on the flat kernel (+0.7 % of that step)
-    // tuning aid: GDL_PLAN="M:OC:BM:BN,..." forces the slab tile of the stride-1 3x3 layers with that many GEMM rows and
-    // output channels (forward and data gradient share it); tools/plan_search.py walks it
-    // 64 -> 64 channels (layer 1): the persistent weights-in-registers kernel, two blocks per CU (80 KB of LDS each at most;
-    // the staged output tile, 128 x 144 bytes, has to fit into one slab buffer)
-    if (!noslab && c64_enabled() && dtype == GDL_BF16 && R == 3 && S == 3 && stride == 1 && pad == 1 && IC == 64 && OC == 64 &&
-        c64_lds_bytes(W, true) <= (size_t)80 * 1024 && (size_t)((C64_BM + 2 * W + 2 + 7) / 8) * 1024 >= (size_t)C64_BM * 144 &&
-        M >= 64 * C64_BM) {
-        // (images too wide for two slab buffers in 80 KB -- the 157-pixel audio layer 1 of the Kinetics-Sounds / VGGSound
-        // shapes -- run it with one)
-        p.single = c64_lds_bytes(W) > (size_t)80 * 1024;
-        static int wide = -1;
-        if (wide < 0) {
-            const char* e = tune_env("GDL_C64_WIDE");  // tuning aid: 0 = wide images stay on the slab kernel
-            wide = e ? atoi(e) : 1;
-        }
-        if (p.single && !wide) {
-            p.single = 0;
-            goto no_c64;
-        }
-        p.slab = 1, p.c64 = 1, p.bm = C64_BM, p.bn = 64, p.lds = c64_lds_bytes(W, p.single != 0);
-        return p;
-    }
-no_c64:
-    if (!noslab && R == 3 && S == 3 && stride == 1 && pad == 1) {
-        static const char* plan_env = tune_env("GDL_PLAN");
-        for (const char* q = plan_env; q && *q;) {
-            int m = 0, oc = 0, bm = 0, bn = 0;
-            if (sscanf(q, "%d:%d:%d:%d", &m, &oc, &bm, &bn) == 4 && m == M && oc == OC && OC % bn == 0 &&
-                (bm == 128 || bm == 256 || (bm == 192 && bn == 128)) && (bn == 64 || bn == 128) && (dtype == GDL_BF16 || bm != 192)) {
-                const bool single = bn == 128 && bm != 128;
-                const size_t lds = slab_lds_bytes(bm, bn, W, IC, dtype, single);
-                if (lds <= (size_t)112 * 1024 && (dtype == GDL_BF16 || !single)) {
-                    p.slab = 1, p.bm = bm, p.bn = bn, p.single = single, p.lds = lds;
-                    return p;
-                }
-            }
-            q = strchr(q, ',');
-            if (q) ++q;
-        }
-    }
-    for (const size_t slab_cap : {(size_t)80 * 1024, (size_t)112 * 1024})
-    if (!noslab && R == 3 && S == 3 && stride == 1 && pad == 1) {
-        // Measured end to end (bench.py, four streams sharing the CUs): the 128-row tile (48 KB of LDS, three
-        // blocks per CU) beats the 256-row one (64 KB, two) by ~1 %, although they tie when run alone.
-        static int slab_bn = -1;
-        if (slab_bn < 0) {
-            const char* e = tune_env("GDL_SLAB_BN");  // tuning aid: 64 = never use the 128-channel tile
-            slab_bn = e ? atoi(e) : 0;
-        }
-        // 128 x 128 tile when the layer is wide enough and still yields a block per CU: the slab is fetched
-        // once per 128 output channels and a K-step carries twice the MFMAs for the same barrier / DMA issue
-        // 128-channel tiles of 192 / 256 rows with ONE slab buffer (bf16): more MFMAs per barrier / weight-tile DMA /
-        // address arithmetic than the 128 x 128 tile and fewer fragment bytes per MFMA (PMC of the 128 x 128 kernel:
-        // MFMA 24 % of a wave's cycles, the rest waits, LDS issue stalls and scalar / vector address work); two blocks
-        // per CU still fit because the next chunk's slab is not double buffered.  Which M-tile wins is mostly a matter
-        // of how the tile count divides by the 512 block slots: measured block times fit T(BM) ~ 130 + BM (256 x 128:
-        // 26.5 us against 17.7 us for 128 x 128 at 128 channels), so pick the smallest rounds(BM) * (130 + BM).
-        if (slab_cfg() != 0 && !slab_bm && dtype == GDL_BF16 && OC % 128 == 0 && slab_cap == (size_t)80 * 1024) {
-            int best_bm = 0;
-            double best = 0.0;
-            for (int bm : {128, 192, 256}) {
-                if (bm == 192 && !(slab_cfg() & 2)) continue;
-                if (bm == 256 && !(slab_cfg() & 1)) continue;
-                const bool single = bm != 128;
-                const size_t lds = slab_lds_bytes(bm, 128, W, IC, dtype, single);
-                if (lds > slab_cap) continue;
-                const long blocks = (long)((M + bm - 1) / bm) * (OC / 128);
-                if (bm != 128 && blocks < slab_big_min()) continue;
-                if (bm == 128 && blocks < slab_bn128_min()) continue;
-                const double rounds = (double)((blocks + 511) / 512);
-                const double cost = rounds * (130.0 + bm);
-                if (!best_bm || cost < best) {
-                    best = cost;
-                    best_bm = bm;
-                }
-            }
-            if (best_bm) {
-                p.slab = 1;
-                p.bm = best_bm;
-                p.bn = 128;
-                p.single = best_bm != 128;
-                p.lds = slab_lds_bytes(best_bm, 128, W, IC, dtype, p.single != 0);
-                return p;
-            }
-        }
-        static int small8 = -1;
-        if (small8 < 0) {
-            // layers too small for 384 blocks of 128 x 128 (here: audio layer 4, M = 3 456) on the 8-wave form of that tile
-            // instead of 128 x 64 tiles: half the blocks, half the filter re-reads.  Alone it is SLOWER (46 -> 54 us), inside the
-            // step faster (5.73 -> 5.67 ms, three A/B rounds): tuning aid, 0 = off
-            const char* e = tune_env("GDL_SLAB_SMALL8");
-            small8 = e ? atoi(e) : 1;
-        }
-        if (small8 && allow_nwv8 && !slab_bm && dtype == GDL_BF16 && OC % 128 == 0 && slab_cap == (size_t)80 * 1024) {
-            const size_t lds = slab_lds_bytes(128, 128, W, IC, dtype);
-            const long blocks = (long)((M + 127) / 128) * (OC / 128);
-            if (lds <= slab_cap && blocks < slab_bn128_min()) {
-                p.slab = 1, p.bm = 128, p.bn = 128, p.lds = lds, p.nwv8 = 1;
-                return p;
-            }
-        }
-        if (!slab_bm && slab_bn != 64 && OC % 128 == 0) {
-            const size_t lds = slab_lds_bytes(128, 128, W, IC, dtype);
-            const long blocks = (long)((M + 127) / 128) * (OC / 128);
-            if (lds <= slab_cap && blocks >= slab_bn128_min()) {
-                p.slab = 1;
-                p.bm = 128;
-                p.bn = 128;
-                p.lds = lds;
-                return p;
-            }
-        }
-        for (int bm : {128, 256}) {
-            if (slab_bm && bm != slab_bm) continue;
-            const size_t lds = slab_lds_bytes(bm, 64, W, IC, dtype);
-            const long blocks = (long)((M + bm - 1) / bm) * (OC / 64);
-            if (lds <= slab_cap && (blocks >= 160 || bm == 128)) {
-                p.slab = 1;
-                p.bm = bm;
-                p.bn = 64;
-                p.lds = lds;
-                return p;
-            }
-        }
-    }
-    TileCfg c = pick_cfg(M, OC, dtype);
-    // plain GEMMs (1x1, stride 1: the Swin encoder's Linears -- the ResNets have none): the 128x128 tile is the faster one
-    // alone (8 DMA pieces per 32 MFMAs instead of 10, each A row gathered for half as many N-tiles), and these run without
-    // a second MFMA-bound stream beside them
-    if (R == 1 && S == 1 && stride == 1 && forced_cfg() == 0 && OC % 128 == 0 && (long)((M + 127) / 128) * (OC / 128) >= 256)
-        c = {128, 128};
-    static int n64bm = -1;
-    if (n64bm < 0) {
-        const char* e = tune_env("GDL_PLAIN_N64_BM");  // tuning aid: M-tile of plain GEMMs whose width is not a multiple of 128
-        n64bm = e ? atoi(e) : 0;
-    }
-    if (R == 1 && S == 1 && stride == 1 && forced_cfg() == 0 && OC % 128 != 0 && n64bm == 128 && c.bm == 256) c = {128, 64};
-    p.slab = 0;
-    p.bm = c.bm;
-    p.bn = c.bn;
-    return p;
-}
-
+// a slab launch of fewer blocks splits K when it is given a workspace (bf16, 128 / 256 / 512 output channels: where the tiles leave
+// CUs idle and the K-loop is long).  Below PS_GRID, the split form of a persistent plan has no more M-tiles than its grid has rows.
+constexpr int SPLITK_BLOCKS = 200;
+static_assert(SPLITK_BLOCKS <= PS_GRID, "split-K blocks");
 // Round 6: the 128-channel-wide slab tiles of 128 / 192 rows (four waves, bf16) run on the persistent pipelined kernel
 // (conv_pslab.h) when its LDS fits: two slab buffers where they fit into 80 KiB (two blocks per CU) -- 96 KiB for a launch that
 // cannot fill two blocks per CU anyway (<= 256 items) --, else one.  (A launch of <= 256 blocks could take 160 KiB for itself; in
@@ -2078,33 +1870,157 @@ static int pslab_mode() {
     }
     return v;
 }
-static ConvPlan plan_conv(int dtype, int M, int OC, int IC, int W, int R, int S, int stride, int pad, bool allow_nwv8 = true) {
-    ConvPlan p = plan_conv_base(dtype, M, OC, IC, W, R, S, stride, pad, allow_nwv8);
-    if (!pslab_mode() || !p.slab || p.c64 || dtype != GDL_BF16 || p.bn != 128 || (p.bm != 128 && p.bm != 192)) return p;
-    if (p.nwv8 && pslab_mode() < 2) return p;
-    const int items = ceil_div(M, p.bm) * (OC / 128);
-    if ((p.bm + 2 * W + 2 + 7) / 8 > 4 * PS_SLAB_PIECES) return p;  // a slab buffer of at most 32 KiB
-    static int big_kb = -1;
-    if (big_kb < 0) {
-        // tuning aid: LDS budget (KiB) of a launch that cannot fill two blocks per CU anyway -- with 160 it takes two slab buffers
-        // (~100 KiB) and leaves the CU's other kernels 60 KiB; 80 = one slab buffer there too
-        const char* e = tune_env("GDL_PSLAB_LDS");
-        big_kb = e ? atoi(e) : 96;  // (step: 160 -> 4.98 ms, 80 -> 4.94, 96 -- two buffers for the 128-row tile of the audio layer 4 only -> 4.92; three A/B rounds)
+
+// The plan of a launch in direction `mode` (GATHER_FWD / GATHER_DGRAD) with options `o`.  Options the persistent kernels cannot
+// serve (bias, GELU output / derivative, a forward addend or ReLU bits) move the launch to the round-5 slab kernel; the row queries
+// plan without options, so such an option may only move a launch that writes no partial rows.  (The persistent kernels' other
+// exclusions -- the stride-2 data gradient's row table, the stem's row segments -- never meet their geometry.)
+static int plan_conv(ConvPlan& p, int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                     const ConvOpts& o = ConvOpts{}) {
+    const bool fwd = mode == GATHER_FWD, bf = dtype == GDL_BF16;
+    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
+    const int M = fwd ? N * P * Q : N * H * W, OC = fwd ? K : C, IC = fwd ? C : K;
+    const bool s1 = R == 3 && S == 3 && stride == 1 && pad == 1;  // the slab kernels' geometry
+    const bool epi = o.bias || o.gelu_out || o.gelu_u || (fwd && (o.addend || o.relu_bits));
+    const bool writes_rows = o.stats || (o.bw && o.bw->y);
+    p = ConvPlan{ConvKind::FLAT, 0, 0, 2, 0, 0, 1, 0};
+    // 64 -> 64 channels (layer 1): the persistent weights-in-registers kernel, two blocks per CU (80 KB of LDS each at most;
+    // the staged output tile, 128 x 144 bytes, has to fit into one slab buffer); images too wide for two slab buffers in 80 KB --
+    // the 157-pixel audio layer 1 of the Kinetics-Sounds / VGGSound shapes -- run it with one
+    if (bf && s1 && IC == 64 && OC == 64 && c64_lds_bytes(W, true) <= (size_t)80 * 1024 &&
+        (size_t)((C64_BM + 2 * W + 2 + 7) / 8) * 1024 >= (size_t)C64_BM * 144 && M >= 64 * C64_BM) {
+        GDL_REQUIRE(!epi || !writes_rows, "conv: an epilogue option would move a launch with partial rows off the 64-channel kernel");
+        if (!epi) {
+            p.kind = ConvKind::C64, p.bm = C64_BM, p.bn = 64, p.nslab = c64_lds_bytes(W) > (size_t)80 * 1024 ? 1 : 2;
+            p.lds = c64_lds_bytes(W, p.nslab == 1), p.grid = p.rows = C64_GRID;
+            return GDL_OK;
+        }
     }
-    const size_t budget = items <= 256 ? (size_t)big_kb * 1024 : (size_t)80 * 1024;
-    int nslab = 0;
-    if (IC > 64 && pslab_lds_bytes(p.bm, W, 2) <= budget)
-        nslab = 2;
-    else if (pslab_lds_bytes(p.bm, W, 1) <= budget)
-        nslab = 1;
-    if (!nslab) return p;
-    // (the 128-row tile of the audio layer 2 -- 396 blocks, two per CU -- had two slab buffers in 80 KiB; with this kernel's staging
-    // and sums rows there is room for one: 23 vs 24 us alone, tools/bench_conv.py -- it keeps the round-5 kernel)
-    if (nslab == 1 && !p.single && IC > 64 && pslab_mode() < 3) return p;  // (GDL_PSLAB=3, tuning aid: the persistent kernel there too -- a tie in the step)
-    p.pslab = 1, p.nwv8 = 0, p.single = nslab == 1, p.lds = pslab_lds_bytes(p.bm, W, nslab), p.grid = pslab_grid(items);
-    return p;
+    // LDS budget of the slab kernel: 80 KB (two blocks per CU); a layer too wide for that (the 79-pixel audio layer 2 of the
+    // Kinetics-Sounds shapes) still runs better on it with one block per CU than on the flat kernel (+0.7 % of that step)
+    for (const size_t slab_cap : {(size_t)80 * 1024, (size_t)112 * 1024}) {
+        if (!s1 || p.kind != ConvKind::FLAT) break;
+        const bool two_per_cu = slab_cap == (size_t)80 * 1024;
+        // 128-channel tiles of 192 rows with ONE slab buffer (bf16): more MFMAs per barrier / weight-tile DMA / address arithmetic
+        // than the 128 x 128 tile and fewer fragment bytes per MFMA (PMC of the 128 x 128 kernel: MFMA 24 % of a wave's cycles, the
+        // rest waits, LDS issue stalls and scalar / vector address work); two blocks per CU still fit because the next chunk's slab
+        // is not double buffered.  Which M-tile wins is mostly a matter of how the tile count divides by the 512 block slots:
+        // measured block times fit T(BM) ~ 130 + BM, so pick the smallest rounds(BM) * (130 + BM).  (The 256-row tile lost inside
+        // the step: tools/experiments/README.md.)
+        if (bf && OC % 128 == 0 && two_per_cu) {
+            double best = 0.0;
+            for (int bm : {128, 192}) {
+                const int nslab = bm == 128 ? 2 : 1;
+                const size_t lds = slab_lds_bytes(bm, 128, W, IC, dtype, nslab == 1);
+                const long blocks = (long)((M + bm - 1) / bm) * (OC / 128);
+                if (lds > slab_cap || blocks < (bm == 128 ? slab_bn128_min() : slab_big_min())) continue;
+                const double cost = (double)((blocks + 511) / 512) * (130.0 + bm);
+                if (p.kind == ConvKind::FLAT || cost < best) p = ConvPlan{ConvKind::SLAB, bm, 128, nslab, lds, 0, 1, 0}, best = cost;
+            }
+            if (p.kind != ConvKind::FLAT) break;
+            // layers too small for 384 blocks of 128 x 128 (here: audio layer 4, M = 3 456) on the 8-wave form of that tile
+            // instead of 128 x 64 tiles: half the blocks, half the filter re-reads.  Alone it is SLOWER (46 -> 54 us), inside the
+            // step faster (5.73 -> 5.67 ms, three A/B rounds)
+            const size_t lds = slab_lds_bytes(128, 128, W, IC, dtype);
+            if (lds <= slab_cap && (long)((M + 127) / 128) * (OC / 128) < slab_bn128_min()) {
+                p = ConvPlan{ConvKind::SLAB8, 128, 128, 2, lds, 0, 1, 0};
+                break;
+            }
+        }
+        // 128 x 128 tile when the layer is wide enough and still yields a block per CU: the slab is fetched once per 128 output
+        // channels and a K-step carries twice the MFMAs for the same barrier / DMA issue.  Else 128 x 64: measured end to end
+        // (bench.py, four streams sharing the CUs) the 128-row tile (48 KB of LDS, three blocks per CU) beats the 256-row one
+        // (64 KB, two) by ~1 %, although they tie when run alone.
+        for (const int bn : {128, 64}) {
+            const size_t lds = slab_lds_bytes(128, bn, W, IC, dtype);
+            if (lds <= slab_cap && (bn == 64 || (OC % 128 == 0 && (long)((M + 127) / 128) * (OC / 128) >= slab_bn128_min()))) {
+                p = ConvPlan{ConvKind::SLAB, 128, bn, 2, lds, 0, 1, 0};
+                break;
+            }
+        }
+    }
+    if (p.kind == ConvKind::FLAT) {
+        const TileCfg c = pick_cfg(M, OC);
+        p.bm = c.bm, p.bn = c.bn;
+        // plain GEMMs (1x1, stride 1: the Swin encoder's Linears -- the ResNets have none): the 128x128 tile is the faster one
+        // alone (8 DMA pieces per 32 MFMAs instead of 10, each A row gathered for half as many N-tiles), and these run without
+        // a second MFMA-bound stream beside them
+        if (R == 1 && S == 1 && stride == 1 && OC % 128 == 0 && (long)((M + 127) / 128) * (OC / 128) >= 256) p.bm = p.bn = 128;
+    }
+    // (the stride-2 data gradient runs over the permuted row table laid out for its M-tile: gather.h)
+    const int mtiles = ceil_div(!fwd && stride == 2 ? dgrad_perm_rows(N, H, W, p.bm) : M, p.bm), ntn = OC / p.bn;
+    p.rows = mtiles;
+    // split-K (an alternative path, off in the engine by default): a launch given a workspace runs on this round-5 slab plan,
+    // whatever the unsplit launch of this geometry runs on, and keeps the unsplit launch's partial rows
+    if (o.split && o.split->ptr && !o.bias && !o.gelu_out && !o.gelu_u && bf && p.kind != ConvKind::FLAT &&
+        (OC == 128 || OC == 256 || OC == 512) && (long)mtiles * ntn < SPLITK_BLOCKS) {
+        const int kpt = IC / 64;
+        while (p.split < 4 && kpt % (2 * p.split) == 0 && (long)mtiles * ntn * (2 * p.split) <= 512) p.split *= 2;
+    }
+    p.grid = xcd_grid(mtiles * ntn * p.split);
+    // the persistent kernel: a slab buffer of at most 32 KiB, and a block that holds several items keeps its N-tile (conv_pslab.h)
+    // only if its item stride, grid / 8, is a multiple of the N-tile count -- other shapes keep the round-5 plan
+    const int mode_ps = pslab_mode();
+    if (mode_ps && bf && p.bn == 128 && (p.kind == ConvKind::SLAB || (p.kind == ConvKind::SLAB8 && mode_ps >= 2)) &&
+        (p.bm + 2 * W + 2 + 7) / 8 <= 4 * PS_SLAB_PIECES) {
+        const int items = mtiles * ntn, grid = pslab_grid(items);
+        // (step: 160 KiB -> 4.98 ms, 80 -> 4.94, 96 -- two buffers for the 128-row tile of the audio layer 4 only -> 4.92; three A/B rounds)
+        const size_t budget = (size_t)(items <= 256 ? 96 : 80) * 1024;
+        const int nslab = IC > 64 && pslab_lds_bytes(p.bm, W, 2) <= budget ? 2 : pslab_lds_bytes(p.bm, W, 1) <= budget ? 1 : 0;
+        // (the 128-row tile of the audio layer 2 -- 396 blocks, two per CU -- had two slab buffers in 80 KiB; with this kernel's staging
+        // and sums rows there is room for one: 23 vs 24 us alone, tools/bench_conv.py -- it keeps the round-5 kernel)
+        if ((items <= grid || (grid / 8) % ntn == 0) && nslab && !(nslab == 1 && p.nslab == 2 && IC > 64)) {
+            if (p.split > 1) {
+                p.rows = grid;
+            } else {
+                GDL_REQUIRE(!epi || !writes_rows, "conv: an epilogue option would move a launch with partial rows off the persistent kernel");
+                if (!epi) p = ConvPlan{ConvKind::PSLAB, p.bm, 128, nslab, pslab_lds_bytes(p.bm, W, nslab), grid, 1, grid};
+            }
+        }
+    }
+    return GDL_OK;
 }
 
+template <typename T, int BM, int BN, int WM, int WN, int MODE>
+static int launch_one(ConvArgs& a, const ConvPlan& pl, hipStream_t st) {
+    using SM = ConvSmem<BM, BN, T>;
+    a.mtiles = ceil_div(a.M, BM);
+    auto kfn = conv_igemm_kernel<T, BM, BN, WM, WN, MODE>;
+    static DevOnce attr_set;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, SM::BYTES);
+        if (e != hipSuccess) return check_hip(e, "hipFuncSetAttribute(conv_igemm)");
+        attr_set = true;
+    }
+    static char pname[96] = "";
+    if (!pname[0])
+        snprintf(pname, sizeof(pname), "gdl::conv_igemm_kernel<%s, %d, %d, %d, %d, %d>", prof_tname<T>(), BM, BN, WM, WN, MODE);
+    ProfScope prof(pname, PROF_MFMA, st, a.flops, true, a.hbm_bytes);
+    hipExtLaunchKernelGGL(kfn, dim3(pl.grid), dim3(256), SM::BYTES, st, prof.e0(), prof.e1(), 0, a);
+    GDL_CHECK_LAUNCH("conv_igemm_kernel");
+    return GDL_OK;
+}
+
+template <typename T, int BM, int BN, int MODE, int NWV = 4>
+static int launch_slab(ConvArgs& a, const ConvPlan& pl, hipStream_t st) {
+    a.mtiles = ceil_div(a.M, BM);
+    auto kfn = conv3x3_slab_kernel<T, BM, BN, MODE, NWV>;
+    static DevOnce attr_set;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return check_hip(e, "hipFuncSetAttribute(conv3x3_slab)");
+        attr_set = true;
+    }
+    static char pname[96] = "";
+    if (!pname[0])
+        snprintf(pname, sizeof(pname), "gdl::conv3x3_slab_kernel<%s, %d, %d, %d, %d>", prof_tname<T>(), BM, BN, MODE, NWV);
+    ProfScope prof(pname, PROF_MFMA, st, a.flops, true, a.hbm_bytes);
+    hipExtLaunchKernelGGL(kfn, dim3(pl.grid), dim3(NWV * 64), pl.lds, st, prof.e0(), prof.e1(), 0, a);
+    GDL_CHECK_LAUNCH("conv3x3_slab_kernel");
+    return GDL_OK;
+}
+
+// (the REQUIREs of the persistent launchers assert what plan_conv guarantees)
 template <int MI, int MODE, bool TWO, bool RICH = false>
 static int launch_pslab(ConvArgs& a, const ConvPlan& pl, hipStream_t st) {
     // (data gradients with an addend or a second BatchNorm partner: the instantiation that carries their registers)
@@ -2168,54 +2084,56 @@ static int launch_c64(ConvArgs& a, size_t lds, hipStream_t st) {
 
 template <typename T, int MODE>
 static int launch_mode(ConvArgs& a, const ConvPlan& pl, hipStream_t st) {
-    if (pl.c64) return launch_c64<MODE>(a, pl.lds, st);
-    if constexpr (std::is_same<T, bf16>::value)
-        if (pl.pslab) {
-            if (pl.single) return pl.bm == 192 ? launch_pslab<3, MODE, false>(a, pl, st) : launch_pslab<2, MODE, false>(a, pl, st);
-            return pl.bm == 192 ? launch_pslab<3, MODE, true>(a, pl, st) : launch_pslab<2, MODE, true>(a, pl, st);
-        }
-    if (pl.slab) {
-        if constexpr (std::is_same<T, bf16>::value)
-            if (pl.bn == 128 && pl.bm == 256) return launch_slab<T, 256, 128, MODE>(a, pl.lds, st);
-        if constexpr (std::is_same<T, bf16>::value)
-            if (pl.bn == 128 && pl.bm == 192) return launch_slab<T, 192, 128, MODE>(a, pl.lds, st);
-        if constexpr (std::is_same<T, bf16>::value)
-            if (pl.bn == 128 && pl.nwv8) return launch_slab<T, 128, 128, MODE, 8>(a, pl.lds, st);
-        if (pl.bn == 128) return launch_slab<T, 128, 128, MODE>(a, pl.lds, st);
-        if (pl.bm == 256) return launch_slab<T, 256, 64, MODE>(a, pl.lds, st);
-        return launch_slab<T, 128, 64, MODE>(a, pl.lds, st);
+    constexpr bool BF = std::is_same<T, bf16>::value;
+    switch (pl.kind) {
+        case ConvKind::C64:
+            if constexpr (BF) return launch_c64<MODE>(a, pl.lds, st);
+            break;
+        case ConvKind::PSLAB:
+            if constexpr (BF) {
+                if (pl.nslab == 1) return pl.bm == 192 ? launch_pslab<3, MODE, false>(a, pl, st) : launch_pslab<2, MODE, false>(a, pl, st);
+                return pl.bm == 192 ? launch_pslab<3, MODE, true>(a, pl, st) : launch_pslab<2, MODE, true>(a, pl, st);
+            }
+            break;
+        case ConvKind::SLAB8:
+            if constexpr (BF) return launch_slab<T, 128, 128, MODE, 8>(a, pl, st);
+            break;
+        case ConvKind::SLAB:
+            if constexpr (BF)
+                if (pl.bm == 192) return launch_slab<T, 192, 128, MODE>(a, pl, st);
+            return pl.bn == 128 ? launch_slab<T, 128, 128, MODE>(a, pl, st) : launch_slab<T, 128, 64, MODE>(a, pl, st);
+        case ConvKind::FLAT:
+            if (pl.bn == 128) return launch_one<T, 128, 128, 2, 2, MODE>(a, pl, st);
+            if (pl.bm == 256) return launch_one<T, 256, 64, 4, 1, MODE>(a, pl, st);
+            if (pl.bm == 128) return launch_one<T, 128, 64, 2, 2, MODE>(a, pl, st);
+            return launch_one<T, 64, 64, 2, 2, MODE>(a, pl, st);
     }
-    if (pl.bn == 128) return launch_one<T, 128, 128, 2, 2, MODE>(a, st);
-    if (pl.bm == 256) return launch_one<T, 256, 64, 4, 1, MODE>(a, st);
-    if (pl.bm == 128) return launch_one<T, 128, 64, 2, 2, MODE>(a, st);
-    return launch_one<T, 64, 64, 2, 2, MODE>(a, st);
+    GDL_REQUIRE(false, "conv: no f32 form of the planned kernel");
 }
 
+// the plan of a launch without options: what the BatchNorm partial-row queries below report (plan_conv cannot fail without options)
+static ConvPlan geometry_plan(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+    ConvPlan p;
+    plan_conv(p, mode, dtype, N, H, W, C, K, R, S, stride, pad);
+    return p;
+}
 // number of M-tiles (= BatchNorm partial rows) the forward kernel of this convolution produces
 int conv_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    const ConvPlan pl = plan_conv(dtype, N * P * Q, K, C, W, R, S, stride, pad);
-    return pl.c64 ? C64_GRID : pl.pslab ? pl.grid : ceil_div(N * P * Q, pl.bm);
+    return geometry_plan(GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad).rows;
 }
-
 // true if the forward of this convolution runs on a persistent kernel (one BatchNorm partial row per block): the in-launch
 // finalize costs a ticket per block LIFE there and is used by default
 bool conv_fwd_persistent(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    const ConvPlan pl = plan_conv(dtype, N * P * Q, K, C, W, R, S, stride, pad);
-    return pl.c64 != 0 || pl.pslab != 0;
+    const ConvKind k = geometry_plan(GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad).kind;
+    return k == ConvKind::C64 || k == ConvKind::PSLAB;
 }
 // partial rows a data gradient with BatchNorm-backward statistics (ops.h BwdStats) writes
 int conv_dgrad_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    const ConvPlan pl = plan_conv(dtype, N * H * W, C, K, W, R, S, stride, pad);
-    if (pl.c64) return C64_GRID;
-    if (pl.pslab) return pl.grid;
-    const int rows = stride == 2 ? dgrad_perm_rows(N, H, W, pl.bm) : N * H * W;
-    return ceil_div(rows, pl.bm);
+    return geometry_plan(GATHER_DGRAD, dtype, N, H, W, C, K, R, S, stride, pad).rows;
 }
 // M-tile of a data gradient (the permuted stride-2 table is laid out for it)
 int conv_dgrad_bm(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    return plan_conv(dtype, N * H * W, C, K, W, R, S, stride, pad).bm;
+    return geometry_plan(GATHER_DGRAD, dtype, N, H, W, C, K, R, S, stride, pad).bm;
 }
 
 // ---------------------------------------------------------------- split-K finish
@@ -2341,40 +2259,19 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(SplitFinArgs f) {
         }
     }
 }
-// splits of a slab launch: only where the tiles leave CUs idle and the K-loop is long (bf16, 128 / 256 / 512 output channels)
-static int splitk_threshold() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = tune_env("GDL_SPLITK_BLOCKS");  // tuning aid: the block count below which a slab launch splits K when it is given a workspace
-        v = e ? atoi(e) : 200;
-    }
-    return v;
-}
-static int plan_ksplit(const ConvPlan& pl, int dtype, int M, int OC, int IC) {
-    if (!pl.slab || pl.c64 || pl.pslab || dtype != GDL_BF16 || splitk_threshold() <= 0) return 1;
-    if (OC != 128 && OC != 256 && OC != 512) return 1;
-    const long blocks = (long)ceil_div(M, pl.bm) * (OC / pl.bn);
-    if (blocks >= splitk_threshold()) return 1;
-    const int kpt = IC / 64;
-    int s = 1;
-    while (s < 4 && kpt % (2 * s) == 0 && kpt / (2 * s) >= 1 && blocks * (2 * s) <= 512) s *= 2;
-    return s;
-}
 size_t conv_split_ws_bytes(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dgrad) {
     const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    const int M = dgrad ? N * H * W : N * P * Q, OC = dgrad ? C : K, IC = dgrad ? K : C;
-    // (split-K belongs to the round-5 slab kernel: a launch that is given a workspace runs on it, below)
-    const ConvPlan pl = plan_conv_base(dtype, M, OC, IC, W, R, S, stride, pad);
-    const int s = plan_ksplit(pl, dtype, M, OC, IC);
-    return s > 1 ? (size_t)s * M * OC * sizeof(float) : 0;
+    const int M = dgrad ? N * H * W : N * P * Q, OC = dgrad ? C : K;
+    SplitWs any{&any, 0};  // a workspace of unknown size: how many ways would a launch given one split?
+    ConvOpts o;
+    o.split = &any;
+    ConvPlan pl;
+    plan_conv(pl, dgrad ? GATHER_DGRAD : GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad, o);
+    return pl.split > 1 ? (size_t)pl.split * M * OC * sizeof(float) : 0;
 }
 
-static int run_conv(int mode, int dtype, const void* in, const void* wt, void* out, const void* addend, float* stats,
-                    const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
-                    hipStream_t st,
-                    const uint8_t* relu_bits = nullptr, const void* dy_ds = nullptr, const void* w_ds = nullptr,
-                    const float* bias = nullptr, void* gelu_out = nullptr, const BwdStats* bw = nullptr,
-                    const BnAcc* sacc = nullptr, const void* gelu_u = nullptr, const SplitWs* split = nullptr) {
+static int run_conv(int mode, int dtype, const void* in, const void* wt, void* out, const void* table, int N, int H, int W, int C,
+                    int K, int R, int S, int stride, int pad, hipStream_t st, const ConvOpts& o = ConvOpts{}) {
     GDL_REQUIRE(dtype == GDL_BF16 || dtype == GDL_F32, "conv: bad dtype %d", dtype);
     GDL_REQUIRE(table, "conv: gather table is null (build it with gdl_conv_build_table)");
     const int bke = (dtype == GDL_BF16) ? 64 : 32;
@@ -2383,6 +2280,8 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
     int rc = gather_geom(mode, dtype, N, H, W, C, K, R, S, stride, pad, &g);
     if (rc) return rc;
     const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
+    const BwdStats* bw = o.bw && o.bw->y ? o.bw : nullptr;
+    const bool sacc = o.sacc && o.sacc->acc;
     ConvArgs a{};
 #ifdef GDL_TIMING
     a.dbg = g_timing_buf;
@@ -2390,21 +2289,21 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
     a.in = in;
     a.wt = wt;
     a.out = out;
-    a.addend = addend;
-    a.bias = bias;
-    a.gelu_out = gelu_out;
-    a.relu_bits = relu_bits;
-    a.stats = stats;
-    a.gelu_u = gelu_u;
-    if (gelu_u) GDL_REQUIRE(mode == GATHER_DGRAD && !(bw && bw->y), "conv: the GELU derivative is a data-gradient option (without BatchNorm sums)");
-    if (sacc && sacc->acc) {
-        GDL_REQUIRE((mode == GATHER_FWD || gelu_u) && !stats, "conv: integer accumulators belong to the forward statistics and to the GELU data gradient's column sums (without partial rows)");
+    a.addend = o.addend;
+    a.bias = o.bias;
+    a.gelu_out = o.gelu_out;
+    a.relu_bits = o.relu_bits;
+    a.stats = o.stats;
+    a.gelu_u = o.gelu_u;
+    if (o.gelu_u) GDL_REQUIRE(mode == GATHER_DGRAD && !bw, "conv: the GELU derivative is a data-gradient option (without BatchNorm sums)");
+    if (sacc) {
+        GDL_REQUIRE((mode == GATHER_FWD || o.gelu_u) && !o.stats, "conv: integer accumulators belong to the forward statistics and to the GELU data gradient's column sums (without partial rows)");
         // without a flag word the channel's SECOND accumulator word is the overflow mark (bnacc.h bn_acc_add): such an accumulator
         // must not also collect sums of squares
-        GDL_REQUIRE(sacc->flag || sacc->s2 == 0.0, "conv: integer accumulators without a flag word take column sums only (s2 = 0)");
-        a.sacc = *sacc;
+        GDL_REQUIRE(o.sacc->flag || o.sacc->s2 == 0.0, "conv: integer accumulators without a flag word take column sums only (s2 = 0)");
+        a.sacc = *o.sacc;
     }
-    if (bw && bw->y) {
+    if (bw) {
         GDL_REQUIRE(mode == GATHER_DGRAD && bw->mean && bw->rstd && bw->partial &&
                         (!bw->y2 || (bw->mean2 && bw->rstd2 && bw->partial2)),
                     "conv: bad BatchNorm-backward statistics arguments");
@@ -2431,21 +2330,22 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
     GDL_REQUIRE(a.OC % 64 == 0, "conv: output channels %d not a multiple of 64", a.OC);
     GDL_REQUIRE(a.M < (1 << 24), "conv: M = %d exceeds 2^24", a.M);
     // the short-K Linears of the Swin branch (plain GEMM, K = 128 / 192, many rows): the streaming kernel (linear_stream.hip)
-    if (a.plain && !stats && !(sacc && sacc->acc) && !relu_bits && !(bw && bw->y) && !gelu_u && !dy_ds &&
-        linear_stream_ok(dtype, a.M, a.IC, a.OC, addend != nullptr))
-        return linear_stream_fwd(in, wt, out, addend, bias, gelu_out, a.M, a.IC, a.OC, st);
-    // the gathered tensor has the output's spatial size for the stride-1 3x3 case the slab kernel serves
-    ConvPlan pl = plan_conv(dtype, a.M, a.OC, a.IC, W, R, S, stride, pad);
+    if (a.plain && !o.stats && !sacc && !o.relu_bits && !bw && !o.gelu_u && !o.dy_ds &&
+        linear_stream_ok(dtype, a.M, a.IC, a.OC, o.addend != nullptr))
+        return linear_stream_fwd(in, wt, out, o.addend, o.bias, o.gelu_out, a.M, a.IC, a.OC, st);
+    ConvPlan pl;
+    rc = plan_conv(pl, mode, dtype, N, H, W, C, K, R, S, stride, pad, o);
+    if (rc) return rc;
     a.flops = 2.0 * (double)N * P * Q * K * C * R * S;  // the convolution's multiply-adds, whatever the direction
     {
         const double esz = dtype == GDL_BF16 ? 2.0 : 4.0;
         a.hbm_bytes = esz * ((double)N * H * W * C + (double)N * P * Q * K + (double)K * C * R * S);
     }
-    if (dy_ds) {
-        GDL_REQUIRE(mode == GATHER_DGRAD && stride == 2 && R == 3 && S == 3 && pad == 1 && w_ds && !pl.slab,
+    if (o.dy_ds) {
+        GDL_REQUIRE(mode == GATHER_DGRAD && stride == 2 && R == 3 && S == 3 && pad == 1 && o.w_ds && pl.kind == ConvKind::FLAT,
                     "conv: the folded downsample branch needs the 3x3 stride-2 pad-1 data gradient");
-        a.in2 = dy_ds;
-        a.wt2 = w_ds;
+        a.in2 = o.dy_ds;
+        a.wt2 = o.w_ds;
         a.in2_bytes = a.in_bytes;  // same [N][P][Q][K] shape as dy
         a.wt2_bytes = (unsigned)((size_t)K * C * esz);
         a.flops += 2.0 * (double)N * P * Q * K * C;
@@ -2456,38 +2356,28 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
         a.tile_order = (const int*)(a.tile_taps + (dgrad_perm_cap(N, H, W) / 64 + 1));
         a.M = dgrad_perm_rows(N, H, W, pl.bm);
     }
-    if (pl.slab) {
+    if (pl.kind != ConvKind::FLAT) {  // the gathered tensor has the output's spatial size for the stride-1 3x3 case
         a.W = W;
-        a.single_slab = pl.single;
+        a.single_slab = pl.nslab == 1;
         a.in_pixels = N * H * W;
         a.slab_rows = pl.bm + 2 * W + 2;
         for (int r = 0; r < 3; ++r)
             for (int s2 = 0; s2 < 3; ++s2)
                 a.pshift[r * 3 + s2] = mode == GATHER_FWD ? (r - 1) * W + (s2 - 1) : (1 - r) * W + (1 - s2);
     }
-    // split-K (an alternative path, off in the engine by default): a launch that is given a workspace and would split runs on the
-    // round-5 slab kernel (its plan), whatever the unsplit launch of this geometry runs on; the partial-row count stays the unsplit
-    // form's (conv_tiles_m / conv_dgrad_tiles_m): the rows past the split form's M-tiles are zeroed
-    const int rows_unsplit = pl.c64 ? C64_GRID : pl.pslab ? pl.grid : 0;
-    int ks = 1;
-    if (split && split->ptr && !bias && !gelu_out && !gelu_u && !dy_ds && !pl.c64) {
-        const ConvPlan plb = pl.pslab ? plan_conv_base(dtype, a.M, a.OC, a.IC, W, R, S, stride, pad) : pl;
-        ks = plan_ksplit(plb, dtype, a.M, a.OC, a.IC);
-        if (ks > 1 && pl.pslab) {
-            pl = plb;
-            a.single_slab = pl.single;
-            a.slab_rows = pl.bm + 2 * W + 2;
-        }
-    }
-    if (ks > 1) {
-        GDL_REQUIRE(split->bytes >= (size_t)ks * a.M * a.OC * sizeof(float), "conv: split-K workspace of %zu bytes, need %zu",
-                    split->bytes, (size_t)ks * a.M * a.OC * sizeof(float));
+    if (pl.split > 1) {
+        const int ks = pl.split, mt = ceil_div(a.M, pl.bm);
+        GDL_REQUIRE(o.split->bytes >= (size_t)ks * a.M * a.OC * sizeof(float), "conv: split-K workspace of %zu bytes, need %zu",
+                    o.split->bytes, (size_t)ks * a.M * a.OC * sizeof(float));
+        // the caller sized its partial rows for the unsplit launch; the finish kernel writes the split form's M-tiles, run_conv
+        // zeroes the rest
+        GDL_REQUIRE(pl.rows >= mt, "conv: split-K form of %d M-tiles for %d partial rows", mt, pl.rows);
         ConvArgs b = a;  // the producing launch leaves fp32 accumulators only
         b.ksplit = ks;
-        b.split_ws = (float*)split->ptr;
+        b.split_ws = (float*)o.split->ptr;
         b.addend = nullptr, b.relu_bits = nullptr, b.stats = nullptr, b.sacc = BnAcc{nullptr, 0.0, 0.0, nullptr};
         b.bw_y = b.bw_y2 = nullptr;
-        const int rc = mode == GATHER_FWD ? launch_mode<bf16, MODE_FWD>(b, pl, st) : launch_mode<bf16, MODE_DGRAD>(b, pl, st);
+        rc = mode == GATHER_FWD ? launch_mode<bf16, MODE_FWD>(b, pl, st) : launch_mode<bf16, MODE_DGRAD>(b, pl, st);
         if (rc != GDL_OK) return rc;
         SplitFinArgs f{};
         f.ws = b.split_ws, f.nsplit = ks, f.M = a.M, f.OC = a.OC, f.BM = pl.bm;
@@ -2495,11 +2385,10 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
         f.bw_y = a.bw_y, f.bw_mean = a.bw_mean, f.bw_rstd = a.bw_rstd, f.bw_partial = a.bw_partial;
         f.bw_y2 = a.bw_y2, f.bw_mean2 = a.bw_mean2, f.bw_rstd2 = a.bw_rstd2, f.bw_partial2 = a.bw_partial2;
         ProfScope prof("gdl::splitk_finish_kernel", PROF_HBM, st, (double)a.M * a.OC * (4.0 * ks + 2.0 * (1 + (a.addend ? 1 : 0) + (a.bw_y ? 1 : 0) + (a.bw_y2 ? 1 : 0))));
-        hipLaunchKernelGGL(splitk_finish_kernel<bf16>, dim3(ceil_div(a.M, pl.bm), a.OC / 64), dim3(256), 0, st, f);
+        hipLaunchKernelGGL(splitk_finish_kernel<bf16>, dim3(mt, a.OC / 64), dim3(256), 0, st, f);
         GDL_CHECK_LAUNCH("splitk_finish_kernel");
-        const int mt = ceil_div(a.M, pl.bm);
-        if (rows_unsplit > mt) {  // the caller sized its partial rows for the unsplit (persistent) form
-            const size_t off = (size_t)mt * a.OC * 2, n = (size_t)(rows_unsplit - mt) * a.OC * 2 * sizeof(float);
+        if (pl.rows > mt) {
+            const size_t off = (size_t)mt * a.OC * 2, n = (size_t)(pl.rows - mt) * a.OC * 2 * sizeof(float);
             for (float* p : {a.stats, a.bw_partial, a.bw_y2 ? a.bw_partial2 : (float*)nullptr})
                 if (p) {
                     hipError_t e = hipMemsetAsync(p + off, 0, n, st);
@@ -2515,8 +2404,9 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
 
 int conv_fwd(int dtype, const void* x, const void* w, void* y, float* bn_partial, const void* table, int N, int H, int W,
              int C, int K, int R, int S, int stride, int pad, hipStream_t st, const BnAcc* sacc, const SplitWs* split) {
-    return run_conv(GATHER_FWD, dtype, x, w, y, nullptr, bn_partial, table, N, H, W, C, K, R, S, stride, pad, st, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, sacc, nullptr, split);
+    ConvOpts o;
+    o.stats = bn_partial, o.sacc = sacc, o.split = split;
+    return run_conv(GATHER_FWD, dtype, x, w, y, table, N, H, W, C, K, R, S, stride, pad, st, o);
 }
 
 // ---- direct stem forward (layout.hip / gather.h): implicit GEMM over the padded NHWC4 input
@@ -2544,7 +2434,7 @@ int conv_stem_tiles_m(int dtype, int n_img, int H, int W) {
     const int M = n_img * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
     if (stem_rows(dtype, W))
         return stem_pers() ? SRP_GRID : ceil_div(n_img * ((H - 1) / 2 + 1) * ceil_div((W - 1) / 2 + 1, 64), 4);
-    return ceil_div(M, pick_cfg(M, 64, dtype).bm);
+    return ceil_div(M, pick_cfg(M, 64).bm);
 }
 int conv_stem_fwd(int dtype, const void* xp, const void* wp, void* y, float* bn_partial, const void* table, int n_img, int H,
                   int W, int Cin, hipStream_t st, const BnAcc* sacc) {
@@ -2617,11 +2507,9 @@ int conv_stem_fwd(int dtype, const void* xp, const void* wp, void* y, float* bn_
         GDL_CHECK_LAUNCH("conv_stem_rows_kernel");
         return GDL_OK;
     }
-    const TileCfg c = pick_cfg(a.M, 64, dtype);
-    ConvPlan pl{};
-    pl.slab = 0;
-    pl.bm = c.bm;
-    pl.bn = c.bn;
+    const TileCfg c = pick_cfg(a.M, 64);
+    const int mt = ceil_div(a.M, c.bm);
+    const ConvPlan pl{ConvKind::FLAT, c.bm, c.bn, 0, 0, xcd_grid(mt * (64 / c.bn)), 1, mt};
     if (dtype == GDL_BF16) return launch_mode<bf16, MODE_FWD>(a, pl, st);
     return launch_mode<float, MODE_FWD>(a, pl, st);
 }
@@ -2629,8 +2517,9 @@ int conv_stem_fwd(int dtype, const void* xp, const void* wp, void* y, float* bn_
 int conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const void* table, int N, int H,
                int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st, const uint8_t* relu_bits,
                const BwdStats* bw, const SplitWs* split) {
-    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, addend, nullptr, table, N, H, W, C, K, R, S, stride, pad, st,
-                    relu_bits, nullptr, nullptr, nullptr, nullptr, bw, nullptr, nullptr, split);
+    ConvOpts o;
+    o.addend = addend, o.relu_bits = relu_bits, o.bw = bw, o.split = split;
+    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, N, H, W, C, K, R, S, stride, pad, st, o);
 }
 
 // dx = dgrad(dy) * gelu'(u), elementwise in the epilogue (u laid out like dx), and the column sums of dx as stored added to
@@ -2639,25 +2528,26 @@ int conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const vo
 int conv_dgrad_gelu(int dtype, const void* dy, const void* w_crsk, void* dx, const void* u, const BnAcc* acc, const void* table,
                     int N, int H, int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st) {
     GDL_REQUIRE(u, "conv_dgrad_gelu: null pointer");
-    const ConvPlan pl = plan_conv(dtype, N * H * W, C, K, W, R, S, stride, pad);
-    GDL_REQUIRE(!pl.c64, "conv_dgrad_gelu: not available on the 64-channel persistent kernel");
-    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, nullptr, nullptr, table, N, H, W, C, K, R, S, stride, pad, st,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, acc, u);
+    ConvOpts o;
+    o.gelu_u = u, o.sacc = acc;
+    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, N, H, W, C, K, R, S, stride, pad, st, o);
 }
 
 // forward with the epilogue's bias / residual: y = conv(x, w) + bias (+ addend), each optional (the Swin Linears)
 int conv_fwd_bias(int dtype, const void* x, const void* w, void* y, const float* bias, const void* addend, void* gelu_out,
                   const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st) {
-    return run_conv(GATHER_FWD, dtype, x, w, y, addend, nullptr, table, N, H, W, C, K, R, S, stride, pad, st, nullptr,
-                    nullptr, nullptr, bias, gelu_out);
+    ConvOpts o;
+    o.addend = addend, o.bias = bias, o.gelu_out = gelu_out;
+    return run_conv(GATHER_FWD, dtype, x, w, y, table, N, H, W, C, K, R, S, stride, pad, st, o);
 }
 
 int conv_dgrad_ds(int dtype, const void* dy, const void* w_crsk, const void* dy_ds, const void* w_ds_ck, void* dx,
                   const void* table, int N, int H, int W, int C, int K, hipStream_t st, const uint8_t* relu_bits,
                   const BwdStats* bw) {
     GDL_REQUIRE(dy_ds && w_ds_ck, "conv_dgrad_ds: null pointer");
-    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, nullptr, nullptr, table, N, H, W, C, K, 3, 3, 2, 1, st,
-                    relu_bits, dy_ds, w_ds_ck, nullptr, nullptr, bw);
+    ConvOpts o;
+    o.relu_bits = relu_bits, o.dy_ds = dy_ds, o.w_ds = w_ds_ck, o.bw = bw;
+    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, N, H, W, C, K, 3, 3, 2, 1, st, o);
 }
 
 }  // namespace gdl

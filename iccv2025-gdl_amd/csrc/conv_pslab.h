@@ -43,9 +43,10 @@ static size_t pslab_lds_bytes(int BM, int W, int nslab) {
     const size_t slab = (size_t)((rows + 7) / 8) * 1024;
     return 2 * (size_t)128 * 128 + nslab * slab + ((rows & 7) ? 0 : 1024) + 4 * PS_STAGE + PS_STAT;
 }
-// grid of a launch: at most PS_GRID blocks, eight equal XCD shares; with several items per block the blocks of an XCD stride by a
-// multiple of 4 (the N-tile counts are 1, 2 and 4: a block keeps its N-tile).  GDL_PSLAB_GRID (tuning aid, also what the operator
-// tests use to run several tiles per block at small sizes) caps it.
+// grid of a launch: at most PS_GRID blocks, eight equal XCD shares; with several items per block the blocks of an XCD stride by
+// grid / 8, a multiple of 4 -- a block keeps its N-tile only if that stride is a multiple of the N-tile count, which plan_conv
+// checks (1, 2 and 4 always; 3 / 5 / 6 only with one item per block).  GDL_PSLAB_GRID (tuning aid, also what the operator tests use
+// to run several tiles per block at small sizes) caps it.
 static int pslab_grid(int items) {
     static int cap = -1;
     if (cap < 0) {

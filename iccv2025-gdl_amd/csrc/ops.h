@@ -45,8 +45,8 @@ struct BwdStats {
 // split-K workspace of the slab convolutions (round 3): where plan_conv's tiles would leave CUs idle (layer 4 of both encoders,
 // the audio layer 3) `ksplit` blocks share an output tile, each multiplies a slice of the input channels and leaves fp32
 // accumulators in the workspace; a finish kernel folds them in fixed order and applies the epilogue (rounding, addend, ReLU
-// bits, statistics).  conv_split_ws_bytes: what a geometry needs (0: that convolution does not split); nullptr / too small a
-// buffer: no split.  bf16 only.
+// bits, statistics).  conv_split_ws_bytes: what a geometry needs (0: that convolution does not split); nullptr: no split, too small
+// a buffer: an error.  bf16 only.
 struct SplitWs {
     void* ptr;
     size_t bytes;
@@ -56,7 +56,9 @@ size_t conv_split_ws_bytes(int dtype, int N, int H, int W, int C, int K, int R, 
 bool linear_stream_ok(int dtype, int M, int K, int N, bool has_addend);
 int linear_stream_fwd(const void* A, const void* W, void* out, const void* addend, const float* bias, void* gelu_out, int M, int K,
                       int N, hipStream_t st);
-// conv_igemm.hip
+// conv_igemm.hip.  The BatchNorm partial rows a forward / data gradient writes (per M-tile, or per block of a persistent kernel):
+// plan_conv's ConvPlan::rows for the geometry alone -- options that move a launch to another kernel only move launches that
+// write no partial rows, and a split-K launch keeps the unsplit count (the rows past its M-tiles are zeroed)
 int conv_dgrad_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
 int conv_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
 int conv_fwd(int dtype, const void* x, const void* w_krsc, void* y, float* bn_partial, const void* table, int N, int H,

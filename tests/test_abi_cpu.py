@@ -79,6 +79,9 @@ def test_slab_planner_at_the_benchmark_shapes():
         assert lib.gdl_conv_bn_tiles(bf16, N, H, W, C, C, 3, 3, 1, 1) == rows, (N, C, H, W)
         assert lib.gdl_conv_dgrad_bn_tiles(bf16, N, H, W, C, C, 3, 3, 1, 1) == rows, (N, C, H, W)
         assert lib.gdl_conv_bn_tiles(f32, N, H, W, C, C, 3, 3, 1, 1) == -(-N * H * W // 128), (N, C, H, W)
+    # 128 -> 384 channels (three N-tiles): 786 items on 512 persistent blocks would change a block's N-tile between its items,
+    # so the shape keeps the 192-row tiles of the round-5 kernel -- 262 M-tiles
+    assert lib.gdl_conv_bn_tiles(bf16, 64, 28, 28, 128, 384, 3, 3, 1, 1) == 262
 
 
 def test_engine_plans_without_gpu_and_reports_errors():

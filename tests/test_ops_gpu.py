@@ -30,7 +30,7 @@ CONV_SHAPES = [
     (2, 64, 9, 6, 128, 1, 2, 0),      # 1x1 stride 2 (downsample)
     (1, 128, 7, 5, 256, 3, 1, 1),     # 64x64, two K-steps per tap
     (10, 64, 33, 31, 128, 3, 1, 1),   # 128x64, ragged tail
-    (3, 64, 120, 115, 64, 3, 1, 1),   # 256x64, ragged tail
+    (3, 64, 120, 115, 64, 3, 1, 1),   # f32: the 128x64 slab tile (324 M-tiles), ragged tail
     (4, 64, 112, 112, 128, 3, 1, 1),  # 256x64, two N-tiles
     (2, 256, 14, 14, 512, 3, 2, 1),   # stride 2, C=256
     (2, 64, 65, 47, 128, 3, 2, 1),    # stride 2 at odd dims (the audio layer-2 geometry): the 9-tap stride-2 weight gradient's edges
@@ -47,6 +47,7 @@ CONV_SHAPES = [
     (20, 256, 14, 14, 256, 3, 1, 1),  # the same with two N-tiles per M-tile and three channel chunks' slab reloads
     (7, 256, 13, 11, 256, 3, 1, 1),   # odd height and width, M = 1001 (ragged last tile), two N-tiles
     (5, 128, 31, 29, 128, 3, 1, 1),   # odd dims at the widest slab of the 192-row tile that still fits 32 KiB (W = 29: 252 rows)
+    (8, 128, 14, 14, 384, 3, 1, 1),   # three N-tiles: persistent only while a block holds one item (39 on 40), else the 8-wave tile
 ]
 
 
@@ -115,6 +116,57 @@ def test_conv_dgrad(shape, dt, with_addend):
     torch.cuda.synchronize()
     got = from_nhwc(dx)
     assert relerr(got, ref) < tol(dt, 2e-6, 4e-3), relerr(got, ref)
+
+
+@pytest.mark.parametrize("shape", [
+    (24, 128, 17, 12, 128),  # planned on the persistent slab kernel without options
+    (4, 64, 56, 56, 64),     # planned on the 64-channel persistent kernel without options
+])
+def test_conv_epilogue_options_on_persistent_shapes(shape):
+    """gdl_conv_fwd_bias (bias + residual + GELU output) and gdl_conv_dgrad_gelu (GELU derivative + fixed-point column sums) on
+    bf16 3x3 stride-1 shapes whose option-free plan is a persistent kernel: those kernels have no such epilogue, the planner moves
+    the launch to the slab kernel (these launches write no BatchNorm partial rows)."""
+    import math
+
+    N, C, H, W, K = shape
+    dt = L.GDL_BF16
+    st = L.cur_stream()
+    x, w = _conv_case(N, C, H, W, K, 3, 1, 1, dt)
+    krsc, crsk = pack_weight(w, dt)
+    erf = np.vectorize(math.erf)
+    # forward: y = conv(x, w) + bias + res, gelu_out = gelu(y as stored)
+    b = rng.standard_normal(K).astype(np.float32)
+    res = quant(rng.standard_normal((N, K, H, W), dtype=np.float32), dt)
+    ref = orc.conv2d_fwd(x, w, 1, 1).astype(np.float64) + b[None, :, None, None] + res
+    xd, bd, rd = to_nhwc(x, dt), dev(b), to_nhwc(res, dt)
+    y, ge = empty((N, H, W, K), dt), empty((N, H, W, K), dt)
+    tab = gather_table(L.GATHER_FWD, dt, N, H, W, C, K, 3, 3, 1, 1)
+    L.call("gdl_conv_fwd_bias", dt, L.ptr(xd), L.ptr(krsc), L.ptr(y), L.ptr(bd), L.ptr(rd), L.ptr(ge), L.ptr(tab), N, H, W, C, K, 3, 3,
+           1, 1, st)
+    torch.cuda.synchronize()
+    got = from_nhwc(y)
+    assert relerr(got, ref) < 4e-3, relerr(got, ref)
+    yy = got.astype(np.float64)
+    assert np.abs(from_nhwc(ge) - 0.5 * yy * (1 + erf(yy / math.sqrt(2)))).max() < 1e-2 * max(1.0, np.abs(yy).max())
+    # data gradient: dx = dgrad(dy, w) * gelu'(u), the column sums of dx as stored into the fixed-point accumulators
+    dy = quant(rng.standard_normal((N, K, H, W), dtype=np.float32), dt)
+    u = quant(rng.standard_normal((N, C, H, W), dtype=np.float32) * 1.5, dt)
+    uu = u.astype(np.float64)
+    dgelu = 0.5 * (1 + erf(uu / math.sqrt(2))) + uu * np.exp(-0.5 * uu * uu) / math.sqrt(2 * math.pi)
+    want = orc.conv2d_bwd_data(dy, w, (N, C, H, W), 1, 1).astype(np.float64) * dgelu
+    M = N * H * W
+    dyd, ud, dx = to_nhwc(dy, dt), to_nhwc(u, dt), empty((N, H, W, C), dt)
+    acc = torch.zeros((C, 2), dtype=torch.int64, device=DEV)
+    scale = 2.0 ** (62 - 7 - max(1, (M - 1).bit_length()))
+    tab = gather_table(L.GATHER_DGRAD, dt, N, H, W, C, K, 3, 3, 1, 1)
+    L.call("gdl_conv_dgrad_gelu", dt, L.ptr(dyd), L.ptr(crsk), L.ptr(dx), L.ptr(ud), L.ptr(acc), scale, L.ptr(tab), N, H, W, C, K, 3, 3,
+           1, 1, st)
+    db = torch.empty(C, device=DEV)
+    L.call("gdl_acc_to_float", L.ptr(acc), C, 1.0 / scale, L.ptr(db), st)
+    torch.cuda.synchronize()
+    got = from_nhwc(dx)
+    assert relerr(got, want) < 4e-3, relerr(got, want)
+    np.testing.assert_allclose(db.cpu().numpy(), got.astype(np.float64).sum((0, 2, 3)), atol=2e-5 * np.sqrt(M))
 
 
 DS_SHAPES = [

@@ -14,11 +14,8 @@ for l in sys.stdin:
 }
 run "base                 " X=1
 run "base (again)         " X=1
-for v in 0 2 3; do run "SLAB_CFG=$v            " GDL_SLAB_CFG=$v; done
 for v in 4 12 16; do run "WGRAD9_MINST=$v        " GDL_WGRAD9_MINST=$v; done
 for v in 128 256 512; do run "WGRAD_BLOCKS=$v        " GDL_WGRAD_BLOCKS=$v; done
-for v in 1 4; do run "CONV_CFG=$v             " GDL_CONV_CFG=$v; done
-run "SLAB_BM=256          " GDL_SLAB_BM=256
 run "EW_V4=0              " GDL_EW_V4=0
 run "STEM_ROWS_BLOCKS=512 " GDL_STEM_ROWS_BLOCKS=512
 run "base (end)           " X=1
