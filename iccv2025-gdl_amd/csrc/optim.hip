@@ -189,6 +189,102 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
     }
 }
 
+// torch.optim.AdamW (_single_tensor_adam, decoupled weight decay) for one element, in torch's order of operations:
+// p *= 1 - lr*wd; m = lerp(m, g, 1 - beta1); v = beta2*v + (1 - beta2)*g*g; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)
+struct AdamWScalars {
+    float decay, b1c, beta2, b2c, step_size, bc2_sqrt, eps;
+};
+
+__device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, const AdamWScalars& s) {
+    p *= s.decay;
+    m += s.b1c * (g - m);
+    v = s.beta2 * v + s.b2c * (g * g);
+    p -= s.step_size * (m / (sqrtf(v) / s.bc2_sqrt + s.eps));
+}
+
+// g *= coef*grad_scale (stored back only when that is not 1, as sgd_kernel), then adamw1
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, const float* __restrict__ stats, float grad_scale,
+                                                    AdamWScalars s, int64_t n) {
+    const float k = (stats ? stats[1] : 1.f) * grad_scale;
+    const bool wb = k != 1.f;
+    const int64_t nv = n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < nv; i += (int64_t)gridDim.x * 256) {
+        float4 pv = ((float4*)p)[i], gv = ((float4*)g)[i], mv = ((float4*)m)[i], vv = ((float4*)v)[i];
+        gv.x *= k;
+        gv.y *= k;
+        gv.z *= k;
+        gv.w *= k;
+        adamw1(pv.x, gv.x, mv.x, vv.x, s);
+        adamw1(pv.y, gv.y, mv.y, vv.y, s);
+        adamw1(pv.z, gv.z, mv.z, vv.z, s);
+        adamw1(pv.w, gv.w, mv.w, vv.w, s);
+        if (wb) ((float4*)g)[i] = gv;
+        ((float4*)m)[i] = mv;
+        ((float4*)v)[i] = vv;
+        ((float4*)p)[i] = pv;
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t i = (nv << 2) + threadIdx.x; i < n; i += 256) {
+            const float gg = g[i] * k;
+            float pp = p[i], mm = m[i], ss = v[i];
+            adamw1(pp, gg, mm, ss, s);
+            if (wb) g[i] = gg;
+            m[i] = mm;
+            v[i] = ss;
+            p[i] = pp;
+        }
+    }
+}
+
+// torch.optim.Adagrad (_single_tensor_adagrad, lr_decay 0) for one element: d = g + wd*p (a temporary, as torch's
+// grad.add(param, alpha=wd) is); s += d*d; p -= lr * d / (sqrt(s) + eps)
+__device__ __forceinline__ void adagrad1(float& p, float g, float& s, float lr, float eps, float wd) {
+    const float d = g + wd * p;
+    s += d * d;
+    p -= lr * (d / (sqrtf(s) + eps));
+}
+
+__global__ __launch_bounds__(256) void adagrad_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ sum,
+                                                      const float* __restrict__ stats, float grad_scale, float lr, float eps,
+                                                      float wd, int64_t n) {
+    const float k = (stats ? stats[1] : 1.f) * grad_scale;
+    const bool wb = k != 1.f;
+    const int64_t nv = n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < nv; i += (int64_t)gridDim.x * 256) {
+        float4 pv = ((float4*)p)[i], gv = ((float4*)g)[i], sv = ((float4*)sum)[i];
+        gv.x *= k;
+        gv.y *= k;
+        gv.z *= k;
+        gv.w *= k;
+        adagrad1(pv.x, gv.x, sv.x, lr, eps, wd);
+        adagrad1(pv.y, gv.y, sv.y, lr, eps, wd);
+        adagrad1(pv.z, gv.z, sv.z, lr, eps, wd);
+        adagrad1(pv.w, gv.w, sv.w, lr, eps, wd);
+        if (wb) ((float4*)g)[i] = gv;
+        ((float4*)sum)[i] = sv;
+        ((float4*)p)[i] = pv;
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t i = (nv << 2) + threadIdx.x; i < n; i += 256) {
+            const float gg = g[i] * k;
+            float pp = p[i], ss = sum[i];
+            adagrad1(pp, gg, ss, lr, eps, wd);
+            if (wb) g[i] = gg;
+            sum[i] = ss;
+            p[i] = pp;
+        }
+    }
+}
+
+// grid of the streaming update kernels: one float4 per thread, grid-stride beyond 4096 blocks of 256
+static int64_t update_blocks(int64_t total) {
+    int64_t blocks = ((total >> 2) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+
 }  // namespace gdl
 
 using namespace gdl;
@@ -305,6 +401,46 @@ int gdl_optim_sgd_step(gdl_optim_t* o, float* params, float* grads, float* momen
     hipLaunchKernelGGL(sgd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, momentum, stats,
                        grad_scale, lr, mu, wd, o->total);
     GDL_CHECK_LAUNCH("sgd_kernel");
+    return GDL_OK;
+}
+
+// The hyperparameters arrive as doubles, the values torch.optim holds: the per-step scalars are derived from them in double
+// and rounded once, as torch rounds a Python scalar into a float32 tensor operation (a float 0.999 alone would move 1 - beta2,
+// the weight of the second moment, by 1.3e-5 relative).
+int gdl_optim_adamw_step(gdl_optim_t* o, float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* stats,
+                         float grad_scale, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                         void* stream) {
+    GDL_REQUIRE(o && params && grads && exp_avg && exp_avg_sq, "optim_adamw_step: null argument");
+    GDL_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
+                "optim_adamw_step: arenas must be 16-byte aligned");
+    GDL_REQUIRE(step >= 1, "optim_adamw_step: step must be >= 1 (the bias corrections count from 1)");
+    AdamWScalars s;
+    s.decay = (float)(1.0 - lr * weight_decay);
+    s.b1c = (float)(1.0 - beta1);
+    s.beta2 = (float)beta2;
+    s.b2c = (float)(1.0 - beta2);
+    s.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
+    s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
+    s.eps = (float)eps;
+    // (p, g, m, v read + p, m, v written = 28 n bytes; the conditional gradient write-back is not charged, as for SGD)
+    ProfScope prof("gdl::adamw_kernel", PROF_HBM, (hipStream_t)stream, (double)o->total * 4.0 * 7);
+    hipLaunchKernelGGL(adamw_kernel, dim3((int)update_blocks(o->total)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                       exp_avg, exp_avg_sq, stats, grad_scale, s, o->total);
+    GDL_CHECK_LAUNCH("adamw_kernel");
+    return GDL_OK;
+}
+
+int gdl_optim_adagrad_step(gdl_optim_t* o, float* params, float* grads, float* state_sum, const float* stats, float grad_scale,
+                           double lr, double eps, double weight_decay, int64_t step, void* stream) {
+    GDL_REQUIRE(o && params && grads && state_sum, "optim_adagrad_step: null argument");
+    GDL_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)state_sum) & 15) == 0,
+                "optim_adagrad_step: arenas must be 16-byte aligned");
+    GDL_REQUIRE(step >= 1, "optim_adagrad_step: step must be >= 1");
+    // (p, g, s read + p, s written = 20 n bytes)
+    ProfScope prof("gdl::adagrad_kernel", PROF_HBM, (hipStream_t)stream, (double)o->total * 4.0 * 5);
+    hipLaunchKernelGGL(adagrad_kernel, dim3((int)update_blocks(o->total)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                       state_sum, stats, grad_scale, (float)lr, (float)eps, (float)weight_decay, o->total);
+    GDL_CHECK_LAUNCH("adagrad_kernel");
     return GDL_OK;
 }
 

@@ -122,6 +122,8 @@ SIGNATURES = {
     "gdl_optim_bind_workspace": ("i", "ppzp"),
     "gdl_optim_grad_stats": ("i", "ppffp" + "pzp"),
     "gdl_optim_sgd_step": ("i", "ppppp" + "ffff" + "p"),
+    "gdl_optim_adamw_step": ("i", "pppppp" + "f" + "ddddd" + "l" + "p"),
+    "gdl_optim_adagrad_step": ("i", "ppppp" + "f" + "ddd" + "l" + "p"),
     "gdl_encoder_create": ("i", "piiiiii"),
     "gdl_encoder_destroy": (None, "p"),
     "gdl_encoder_side_stream": ("i", "pi"),

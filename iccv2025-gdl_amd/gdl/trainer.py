@@ -9,6 +9,7 @@ junction form below):
             -> fusion head forward (all three logit sets), 3x cross-entropy, gradient of fc_out from loss_f alone
   then on A: fused grad statistics (total norm -> clip coefficient, per-encoder sum mean|g|)  (main_dgl.py:129-143)
              fused clip + SGD(momentum, weight decay) over the flat parameter arena            (:154)
+             (or AdamW / Adagrad: `optimizer`, the script's --optimizer switch, :248-259)
 Junction form (other heads, the non-DGL step, and -- until a multi-GPU run has validated the early form's collective order --
 every data-parallel run):
   audio encoder forward  (stream A)  ||  visual encoder forward (stream V)
@@ -65,6 +66,16 @@ class _SwinAdapter:
         self.eng.backward(self._dfeat, list(grads), phase=phase)
 
 
+# The optimizers of main_dgl.py's `--optimizer` switch (:248-259), keyed by the script's own strings, and what it builds for
+# each: SGD(momentum=0.9, weight_decay=1e-4), Adagrad(lr) and AdamW(lr, betas=(0.9, 0.999)) -- the latter two with torch's
+# defaults for everything else.  These are the reference's values, not options; `weight_decay` may be overridden.
+OPTIMIZERS = ("sgd", "Adam", "AdaGrad")
+DEFAULT_WEIGHT_DECAY = {"sgd": 1e-4, "Adam": 1e-2, "AdaGrad": 0.0}
+ADAM_BETAS = (0.9, 0.999)
+ADAM_EPS = 1e-8
+ADAGRAD_EPS = 1e-10
+ADAGRAD_INITIAL_ACCUMULATOR = 0.0
+
 _CHAIN_STREAMS = {}
 
 
@@ -77,10 +88,17 @@ def _chain_streams(device):
 
 
 class DGLTrainer:
-    def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=1e-4, max_norm=40.0, mode="dgl", dtype=None,
-                 process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None):
+    def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
+                 process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd"):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
-        RCCL communicator (gdl_comm_*), bootstrapped through `process_group`."""
+        RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
+        optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
+        None = the reference's value for that optimizer (DEFAULT_WEIGHT_DECAY); `momentum` applies to "sgd" only."""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"DGLTrainer: optimizer must be one of {OPTIMIZERS} (main_dgl.py --optimizer), got {optimizer!r}")
+        self.optimizer = optimizer
+        if weight_decay is None:
+            weight_decay = DEFAULT_WEIGHT_DECAY[optimizer]
         self.lib = L.load()
         self.model = model
         self.mode = mode
@@ -157,7 +175,15 @@ class DGLTrainer:
         group = [0] * nf + [1] * 60 + [2] * self.nv
         self.params = torch.empty(o, device=self.device)
         self.grads = torch.zeros(o, device=self.device)
-        self.momentum = torch.zeros(o, device=self.device)
+        # optimizer state arenas (the parameter arena's layout), only those of the chosen optimizer
+        self.momentum = self.exp_avg = self.exp_avg_sq = self.state_sum = None
+        if optimizer == "sgd":
+            self.momentum = torch.zeros(o, device=self.device)
+        elif optimizer == "Adam":
+            self.exp_avg = torch.zeros(o, device=self.device)
+            self.exp_avg_sq = torch.zeros(o, device=self.device)
+        else:
+            self.state_sum = torch.full((o,), ADAGRAD_INITIAL_ACCUMULATOR, device=self.device)
         self.pviews, self.gviews = [], []
         for i, (_, p) in enumerate(named):
             v = self.params[offs[i]:offs[i + 1]].view(p.shape)
@@ -186,7 +212,7 @@ class DGLTrainer:
             # Replica state follows rank 0 (parameters, momentum, BatchNorm running statistics / counters): a seed
             # that differs between ranks or a rank-0-only checkpoint load must not diverge silently.  fc_auxi (and the
             # gated head's fc_x / fc_y) live outside the arena: they are never updated but still part of the state.
-            self.reducer.sync_state([self.params, self.momentum] + self._replica_buffers())
+            self.reducer.sync_state([self.params] + list(self._opt_state().values()) + self._replica_buffers())
         h = ctypes.c_void_p()
         so = (ctypes.c_int64 * len(offs))(*offs)
         sg = (ctypes.c_int32 * len(group))(*group)
@@ -225,21 +251,37 @@ class DGLTrainer:
         if self.reducer is not None:
             self.reducer.broadcast_buffers(self._replica_buffers())
 
+    def _opt_state(self):
+        """{name: arena} of the chosen optimizer's state: momentum (sgd), exp_avg + exp_avg_sq (Adam), state_sum (AdaGrad)."""
+        names = {"sgd": ("momentum",), "Adam": ("exp_avg", "exp_avg_sq"), "AdaGrad": ("state_sum",)}[self.optimizer]
+        return {n: getattr(self, n) for n in names}
+
     def state_dict(self):
         """Optimizer-side state a reference checkpoint keeps besides model.state_dict() (optimizer.state_dict() /
-        scheduler, main_dgl.py:372): momentum arena, learning rate, step count.  In data-parallel mode the BatchNorm
-        buffers are first made rank 0's, so model.state_dict() taken next is the reference's replica-0 state."""
+        scheduler, main_dgl.py:372): the optimizer's kind and state arenas, learning rate, step count (which the Adam bias
+        corrections count from).  In data-parallel mode the BatchNorm buffers are first made rank 0's, so model.state_dict()
+        taken next is the reference's replica-0 state."""
         self.sync_replicas()
-        return {"momentum": self.momentum.detach().clone(), "lr": self.lr, "steps": self.steps, "names": list(self.names),
-                "offsets": list(self.offsets), "mu": self.mu, "weight_decay": self.wd}
+        return {"optimizer": self.optimizer, **{k: v.detach().clone() for k, v in self._opt_state().items()}, "lr": self.lr,
+                "steps": self.steps, "names": list(self.names), "offsets": list(self.offsets), "mu": self.mu,
+                "weight_decay": self.wd}
 
     def load_state_dict(self, sd):
         if list(sd["offsets"]) != list(self.offsets) or list(sd["names"]) != list(self.names):
             raise L.GdlError("DGLTrainer.load_state_dict: the checkpoint's parameter layout differs from this model's")
-        self.momentum.copy_(sd["momentum"].to(self.device))
+        kind = sd.get("optimizer", "sgd")  # (checkpoints written before the optimizer switch are SGD's)
+        if kind != self.optimizer:
+            raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint holds {kind!r} state, this trainer runs "
+                             f"{self.optimizer!r}")
+        state = self._opt_state()
+        for k, v in state.items():
+            v.copy_(sd[k].to(self.device))
         self.lr, self.steps = float(sd["lr"]), int(sd["steps"])
         if self.reducer is not None:  # the model's parameters alias the arena: whatever rank 0 loaded is the truth
-            self.reducer.sync_state([self.params, self.momentum] + self._replica_buffers())
+            # (the step count too: the Adam bias corrections are derived from it; and the learning rate)
+            hp = torch.tensor([self.lr, float(self.steps)], dtype=torch.float64, device=self.device)
+            self.reducer.sync_state([self.params] + list(state.values()) + self._replica_buffers() + [hp])
+            self.lr, self.steps = float(hp[0].item()), int(hp[1].item())
 
     def close(self):
         """Releases what the trainer owns outside PyTorch's allocator: the optimizer descriptor and, for
@@ -509,7 +551,7 @@ class DGLTrainer:
         self._finish_step(main, st)
 
     def _finish_step(self, main, st):
-        """Joins the chains (and the collectives), then gradient statistics + clip + SGD on `main`."""
+        """Joins the chains (and the collectives), then gradient statistics + clip + the optimizer's update on `main`."""
         red = self.reducer
         main.wait_stream(self.s_a)
         main.wait_stream(self.s_v)
@@ -519,8 +561,16 @@ class DGLTrainer:
         gs = 1.0 / self.world
         L.call("gdl_optim_grad_stats", self.opt, L.ptr(self.grads), self.max_norm, gs, L.ptr(self.stats),
                L.ptr(self.opt_ws), self.opt_ws_bytes, st)
-        L.call("gdl_optim_sgd_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.momentum),
-               L.ptr(self.stats), gs, self.lr, self.mu, self.wd, st)
+        if self.optimizer == "sgd":
+            L.call("gdl_optim_sgd_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.momentum),
+                   L.ptr(self.stats), gs, self.lr, self.mu, self.wd, st)
+        elif self.optimizer == "Adam":
+            L.call("gdl_optim_adamw_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.exp_avg),
+                   L.ptr(self.exp_avg_sq), L.ptr(self.stats), gs, self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, self.wd,
+                   self.steps + 1, st)
+        else:
+            L.call("gdl_optim_adagrad_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.state_sum),
+                   L.ptr(self.stats), gs, self.lr, ADAGRAD_EPS, self.wd, self.steps + 1, st)
         self._mark(main, "end")
         if self.stats_log is not None and self.stats_log_pos is not None and self.stats_log_pos < self.stats_log.shape[0]:
             self.stats_log[self.stats_log_pos].copy_(self.stats[:2], non_blocking=True)

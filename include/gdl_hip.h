@@ -371,6 +371,16 @@ GDL_API int gdl_frames_normalize(const uint8_t* frames, int64_t n_img, int H, in
  * gdl_optim_sgd_step: g *= clip_coef*grad_scale (written back); d = g + wd*p;
  *   m = mu*m + d; p -= lr*m  (momentum arena starts at zero, which reproduces
  *   torch's first-step `buf = d`).
+ * gdl_optim_adamw_step: optim.AdamW(lr, betas=(beta1, beta2), eps, weight_decay) as main_dgl.py:255-256 builds it for
+ *   `--optimizer Adam` (torch's _single_tensor_adam, decoupled weight decay, no amsgrad), in torch's order:
+ *   g *= clip_coef*grad_scale (written back); p *= 1 - lr*wd; m += (1 - beta1)*(g - m); v = beta2*v + (1 - beta2)*g*g;
+ *   p -= lr/(1 - beta1^step) * m / (sqrt(v)/sqrt(1 - beta2^step) + eps).  Both moment arenas start at zero.
+ * gdl_optim_adagrad_step: optim.Adagrad(lr, eps, weight_decay) as main_dgl.py:252-253 builds it for `--optimizer AdaGrad`
+ *   (lr_decay 0): g *= clip_coef*grad_scale (written back); d = g + wd*p (not written back); s += d*d;
+ *   p -= lr * d / (sqrt(s) + eps).  The accumulator arena starts at zero (torch's initial_accumulator_value).
+ *   Both: `step` counts the updates, the first is 1 (step < 1 is an error); the bias corrections are derived from it, and
+ *   every per-step scalar from the double hyperparameters, in double on the host, then rounded to float once.  One launch
+ *   over the whole arena, no host sync; the clipped gradient is written back only where clip_coef*grad_scale != 1.
  * The object owns no device memory: gdl_optim_create only builds host tables; `ws` (gdl_optim_workspace_bytes, 16-byte
  * aligned, caller-owned) holds the descriptor tables in its head -- uploaded, ordered on `stream`, the first time
  * gdl_optim_grad_stats is called with that pointer -- and the per-chunk partial sums behind them.  Keep the workspace intact
@@ -388,6 +398,11 @@ GDL_API int gdl_optim_bind_workspace(gdl_optim_t* o, void* ws, size_t ws_bytes, 
 GDL_API int gdl_optim_stats_len(const gdl_optim_t* o); /* 4 + 2*nseg floats */
 GDL_API int gdl_optim_sgd_step(gdl_optim_t* o, float* params, float* grads, float* momentum, const float* stats,
                                float grad_scale, float lr, float mu, float wd, void* stream);
+GDL_API int gdl_optim_adamw_step(gdl_optim_t* o, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                                 const float* stats, float grad_scale, double lr, double beta1, double beta2, double eps,
+                                 double weight_decay, int64_t step, void* stream);
+GDL_API int gdl_optim_adagrad_step(gdl_optim_t* o, float* params, float* grads, float* state_sum, const float* stats,
+                                   float grad_scale, double lr, double eps, double weight_decay, int64_t step, void* stream);
 
 /* ------------------------------------------------------------------ ResNet18 encoder engine
  * `resnet18(modality, args)` / ResNet.forward (backbone.py:75-201, 255-257) plus the
