@@ -353,6 +353,18 @@ int gdl_frames_normalize(const uint8_t* frames, int64_t n_img, int H, int W, con
     GDL_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "frames_normalize: zero std");
     return frames_normalize(frames, (size_t)n_img, H, W, mean, std, out, (hipStream_t)stream);
 }
+int gdl_frames_resized_crop_box_ok(int box_h, int box_w, int out_h, int out_w) { return resized_crop_box_ok(box_h, box_w, out_h, out_w); }
+int gdl_frames_resized_crop(const uint8_t* src, size_t src_bytes, const int64_t* desc, int n_img, int B, int T, int out_h, int out_w,
+                            const float* mean, const float* std, float* out, void* stream) {
+    GDL_REQUIRE(src && desc && out && mean && std && src_bytes > 0, "frames_resized_crop: bad arguments");
+    GDL_REQUIRE(((uintptr_t)src & 3) == 0 && ((uintptr_t)desc & 7) == 0, "frames_resized_crop: src must be 4-byte, desc 8-byte aligned");
+    GDL_REQUIRE(n_img > 0 && B > 0 && T > 0 && (int64_t)B * T == n_img, "frames_resized_crop: n_img (%d) must be B * T (%d * %d)", n_img, B, T);
+    GDL_REQUIRE(out_h > 0 && out_w > 0, "frames_resized_crop: output size %d x %d must be positive", out_h, out_w);
+    GDL_REQUIRE(resized_crop_box_ok(1, 1, out_h, out_w), "frames_resized_crop: output size %d x %d does not fit the kernel's tables", out_h, out_w);
+    GDL_REQUIRE((int64_t)n_img * ((out_h + 15) / 16) < (int64_t)1 << 31, "frames_resized_crop: too many images for one launch");
+    GDL_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "frames_resized_crop: zero std");
+    return frames_resized_crop(src, src_bytes, (const long long*)desc, n_img, T, out_h, out_w, mean, std, out, (hipStream_t)stream);
+}
 int gdl_softmax_ce3(const float* logits0, const float* logits1, const float* logits2, const int64_t* labels, float scale0,
                     float scale1, float scale2, float* losses, float* dlogits0, float* dlogits1, float* dlogits2, int B,
                     int n_classes, void* stream) {

@@ -190,6 +190,9 @@ int logspec_frames(int L, int hop);
 int logspec(const float* wave, int B, int L, int n_fft, int hop, int reflect, float* out, hipStream_t st);
 int frames_normalize(const unsigned char* in, size_t n_img, int H, int W, const float* mean, const float* std, float* out,
                      hipStream_t st);
+int resized_crop_box_ok(int box_h, int box_w, int out_h, int out_w);
+int frames_resized_crop(const unsigned char* src, size_t src_bytes, const long long* desc, int n_img, int T, int out_h, int out_w,
+                        const float* mean, const float* std, float* out, hipStream_t st);
 int eval_count(const float* out, const float* out_a, const float* out_v, const int64_t* labels, int B, int n, int64_t* num,
                int64_t* acc, int64_t* acc_a, int64_t* acc_v, hipStream_t st);
 int softmax_ce_multi(int nsets, const float* const* logits, const int64_t* labels, const float* scales, float* losses,

@@ -114,6 +114,8 @@ SIGNATURES = {
     "gdl_logspec_frames": ("i", "ii"),
     "gdl_logspec": ("i", "p" + "iiiii" + "pp"),
     "gdl_frames_normalize": ("i", "p" + "lii" + "ppp" + "p"),
+    "gdl_frames_resized_crop_box_ok": ("i", "iiii"),
+    "gdl_frames_resized_crop": ("i", "pzp" + "iiiii" + "ppp" + "p"),
     "gdl_eval_count": ("i", "pppp" + "ii" + "pppp" + "p"),
     "gdl_optim_create": ("i", "pppi"),
     "gdl_optim_destroy": (None, "p"),

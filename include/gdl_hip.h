@@ -352,13 +352,39 @@ GDL_API int gdl_eval_count(const float* out, const float* out_a, const float* ou
  *     tensor the DataLoader yields.  pad_mode: how the n_fft/2 samples either side are made up -- librosa >= 0.10
  *     pads with zeros (GDL_PAD_CONSTANT), older releases reflect (GDL_PAD_REFLECT); the reference does not pin a version.
  *   gdl_frames_normalize: transforms.ToTensor() + Normalize(mean, std) (CramedDataset.py:77-81): uint8 [n_img][H][W][3]
- *     -> float32 [n_img][3][H][W], ((x / 255) - mean[c]) / std[c]; mean / std: 3 host floats each. */
+ *     -> float32 [n_img][3][H][W], ((x / 255) - mean[c]) / std[c]; mean / std: 3 host floats each.
+ *   gdl_frames_resized_crop: the datasets' whole visual transform in one launch -- training: RandomResizedCrop(size),
+ *     RandomHorizontalFlip(), ToTensor(), Normalize(mean, std); evaluation: Resize((size, size)), ToTensor(), Normalize
+ *     (CramedDataset.py:76-88) -- for boxes and flips the caller has drawn on the host.
+ *     src: n_img decoded frames packed in one uint8 device buffer of src_bytes bytes (4-byte aligned), each HWC with
+ *     3 channels and a row pitch of 3 * width; frames may differ in size.  desc: int64 [n_img][8] in device memory,
+ *       { byte offset of the frame in src, height, width, box top, box left, box height, box width, flip (0 / 1) };
+ *     the whole frame as the box is Resize.  Image n is frame t = n % T of sample b = n / T; out: float32
+ *     [B][3][T][out_h][out_w] (the datasets' permute(1, 0, 2, 3) is folded into the store; T = 1: [n_img][3][out_h][out_w]).
+ *     Arithmetic: the box is cropped first, so pixels outside it never contribute; then Pillow's ImagingResample with
+ *     the bilinear filter, which is what Resize runs on a PIL image: separable, the horizontal pass first, then the
+ *     vertical, the intermediate image rounded to uint8.  Per output index i of a pass in -> out: scale = in / out,
+ *     filterscale = support = max(1, scale), center = (i + 0.5) * scale, taps x from max(0, int(center - support + 0.5))
+ *     up to min(in, int(center + support + 0.5)), weight triangle((x - center + 0.5) / filterscale), the weights
+ *     normalised to sum 1 in double precision and rounded to 22 fractional bits, k = int(0.5 + w * 2^22);
+ *     result = clip((2^21 + sum k[x] * pixel[x]) >> 22, 0, 255) in int32.  Then out[.., w] = resized[.., flip ? out_w-1-w : w],
+ *     ((x / 255) - mean[c]) / std[c] as gdl_frames_normalize.  The result is bit-identical to that recipe
+ *     (tests/resize_ref.py restates it in NumPy); against torch's antialiased uint8 CPU resize it differs by at most one grey level
+ *     on about 1 % of the pixels (docs/parity_log.md).
+ *     Limits: frames and boxes up to 65535 a side; a box must pass gdl_frames_resized_crop_box_ok(box_h, box_w, out_h,
+ *     out_w) (1 = fits): the kernel keeps the coefficient tables, one source row of the box and the rows of one output
+ *     row's vertical taps in 40 KB of LDS -- for a 224 x 224 output a 1080 x 1920 box fits, 16:9 boxes up to about 2200
+ *     columns wide do, a 2160 x 3840 box does not.  The caller checks boxes (it has them on the host; gdl.data does); the kernel clamps a box into its frame,
+ *     and an image whose frame does not lie inside src or whose box does not fit is written as NaN, never read out of bounds. */
 #define GDL_PAD_CONSTANT 0
 #define GDL_PAD_REFLECT 1
 GDL_API int gdl_logspec_frames(int n_samples, int hop);
 GDL_API int gdl_logspec(const float* wave, int B, int n_samples, int n_fft, int hop, int pad_mode, float* out, void* stream);
 GDL_API int gdl_frames_normalize(const uint8_t* frames, int64_t n_img, int H, int W, const float* mean, const float* std,
                                  float* out, void* stream);
+GDL_API int gdl_frames_resized_crop_box_ok(int box_h, int box_w, int out_h, int out_w);
+GDL_API int gdl_frames_resized_crop(const uint8_t* src, size_t src_bytes, const int64_t* desc, int n_img, int B, int T, int out_h,
+                                    int out_w, const float* mean, const float* std, float* out, void* stream);
 
 /* ------------------------------------------------------------------ clip + grad stats + SGD
  * clip_grad_norm_(params, 40, 2) (main_dgl.py:129), the logged
