@@ -312,6 +312,23 @@ int gdl_head_gated_bwd(const float* x, const float* y, const float* hx, const fl
     return head_gated_bwd(x, y, hx, hy, W1, W2, Wo, g_x_out, g_y_out, g_out, uni_in_dw, dx, dy, dW1, db1, dW2, db2, dWo, dbo, ws, B,
                           n_classes, (hipStream_t)stream);
 }
+int gdl_head_gated_joint_fwd(const float* x, const float* y, const float* W1, const float* b1, const float* W2, const float* b2,
+                             const float* Wo, const float* bo, float* hx, float* hy, float* out, int x_gate, int B, int n_classes,
+                             void* stream) {
+    GDL_REQUIRE(x && y && W1 && b1 && W2 && b2 && Wo && bo && hx && hy && out && B > 0 && n_classes > 0,
+                "head_gated_joint_fwd: bad arguments");
+    return head_gated_joint_fwd(x, y, W1, b1, W2, b2, Wo, bo, hx, hy, out, x_gate != 0, B, n_classes, (hipStream_t)stream);
+}
+int gdl_head_gated_joint_bwd(const float* x, const float* y, const float* hx, const float* hy, const float* W1, const float* W2,
+                             const float* Wo, const float* g_out, int x_gate, float* dx, float* dy, float* dW1, float* db1,
+                             float* dW2, float* db2, float* dWo, float* dbo, float* ws, int B, int n_classes, void* stream) {
+    GDL_REQUIRE(x && y && hx && hy && W1 && W2 && Wo && g_out && ws && B > 0 && n_classes > 0, "head_gated_joint_bwd: bad arguments");
+    GDL_REQUIRE((dx != nullptr) == (dy != nullptr) && (dWo != nullptr) == (dbo != nullptr), "head_gated_joint_bwd: dx/dy, dWo/dbo pairs");
+    GDL_REQUIRE((dW1 != nullptr) == (db1 != nullptr) && (dW1 != nullptr) == (dW2 != nullptr) && (dW1 != nullptr) == (db2 != nullptr),
+                "head_gated_joint_bwd: dW1/db1/dW2/db2 come together");
+    return head_gated_joint_bwd(x, y, hx, hy, W1, W2, Wo, g_out, x_gate != 0, dx, dy, dW1, db1, dW2, db2, dWo, dbo, ws, B, n_classes,
+                                (hipStream_t)stream);
+}
 size_t gdl_head_film_workspace_bytes(int B) { return head_film_ws_bytes(B); }
 int gdl_head_film_fwd(const float* x, const float* y, const float* Wfc, const float* bfc, const float* Wo, const float* bo,
                       float* hidden, float* out, float* x_out, float* y_out, int B, int n_classes, void* ws, size_t ws_bytes,
@@ -328,6 +345,20 @@ int gdl_head_film_bwd(const float* x, const float* y, const float* Wfc, const fl
                 "head_film_bwd: dx/dy, dWfc/dbfc, dWo/dbo come in pairs");
     return head_film_bwd(x, y, Wfc, Wo, hidden, g_x_out, g_y_out, g_out, uni_in_dw, dx, dy, dWfc, dbfc, dWo, dbo, B, n_classes,
                          ws, ws_bytes, (hipStream_t)stream);
+}
+int gdl_head_film_joint_fwd(const float* x, const float* y, const float* Wfc, const float* bfc, const float* Wo, const float* bo,
+                            float* hidden, float* out, int B, int n_classes, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(x && y && Wfc && bfc && Wo && bo && hidden && out && n_classes > 0, "head_film_joint_fwd: bad arguments");
+    return head_film_joint_fwd(x, y, Wfc, bfc, Wo, bo, hidden, out, B, n_classes, ws, ws_bytes, (hipStream_t)stream);
+}
+int gdl_head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const float* Wo, const float* hidden,
+                            const float* g_out, float* dx, float* dy, float* dWfc, float* dbfc, float* dWo, float* dbo, int B,
+                            int n_classes, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(x && y && Wfc && Wo && hidden && g_out && n_classes > 0, "head_film_joint_bwd: bad arguments");
+    GDL_REQUIRE((dx != nullptr) == (dy != nullptr) && (dWfc != nullptr) == (dbfc != nullptr) && (dWo != nullptr) == (dbo != nullptr),
+                "head_film_joint_bwd: dx/dy, dWfc/dbfc, dWo/dbo come in pairs");
+    return head_film_joint_bwd(x, y, Wfc, Wo, hidden, g_out, dx, dy, dWfc, dbfc, dWo, dbo, B, n_classes, ws, ws_bytes,
+                               (hipStream_t)stream);
 }
 int gdl_eval_count(const float* out, const float* out_a, const float* out_v, const int64_t* labels, int B, int n_classes,
                    int64_t* num, int64_t* acc, int64_t* acc_a, int64_t* acc_v, void* stream) {

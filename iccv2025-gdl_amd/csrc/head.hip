@@ -695,6 +695,92 @@ int head_gated_bwd(const float* x, const float* y, const float* hx, const float*
     return GDL_OK;
 }
 
+// ---------------------------------------------------------------- GatedFusion, trained jointly (fusion_modules.py:181-210)
+//   hx = fc_x(x), hy = fc_y(y);  x_gate: out = fc_out(sigmoid(hx) * hy),  else: out = fc_out(hx * sigmoid(hy))
+// One cross-entropy on `out` reaches all six tensors and both feature vectors (no detach anywhere).
+// grid = B: the fused logits alone; per class the same products, lane order and butterfly as gated_out_kernel's `out`
+// (x_gate = 1: bit-identical to the DGL head's `out`)
+__global__ __launch_bounds__(256) void gated_joint_out_kernel(const float* __restrict__ hx, const float* __restrict__ hy,
+                                                              const float* __restrict__ Wo, const float* __restrict__ bo,
+                                                              float* __restrict__ out, int x_gate, int n) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* gate = (x_gate ? hx : hy) + (size_t)b * HD;
+    const float* val = (x_gate ? hy : hx) + (size_t)b * HD;
+    float gz[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float a = gate[lane + 64 * i], c = val[lane + 64 * i];
+        const float ga = sigmoidf_(a);
+        gz[i] = ga * c;
+    }
+    for (int j = wave; j < n; j += 4) {
+        const float* w = Wo + (size_t)j * HD;
+        float pz = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float wv = w[lane + 64 * i];
+            pz += wv * gz[i];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pz += __shfl_xor(pz, o);
+        if (lane == 0) out[(size_t)b * n + j] = pz + bo[j];
+    }
+}
+int head_gated_joint_fwd(const float* x, const float* y, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* Wo, const float* bo, float* hx, float* hy, float* out, int x_gate, int B, int n,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(gated_hidden_kernel, dim3(B, 2), dim3(256), 0, st, x, y, W1, b1, W2, b2, hx, hy);
+    GDL_CHECK_LAUNCH("gated_hidden_kernel");
+    hipLaunchKernelGGL(gated_joint_out_kernel, dim3(B), dim3(256), 0, st, hx, hy, Wo, bo, out, x_gate, n);
+    GDL_CHECK_LAUNCH("gated_joint_out_kernel");
+    return GDL_OK;
+}
+// grid = B, a thread per hidden unit j:  dm = sum_c g_out[b][c] Wo[c][j]  (classes in ascending order), s = sigmoid(gate[j]):
+//   d(value)[j] = dm * s,   d(gate)[j] = dm * value[j] * s (1 - s)          (gate = hx, value = hy if x_gate, else swapped)
+__global__ __launch_bounds__(256) void gated_joint_dh_kernel(const float* __restrict__ hx, const float* __restrict__ hy,
+                                                             const float* __restrict__ Wo, const float* __restrict__ g_out,
+                                                             float* __restrict__ dhx, float* __restrict__ dhy, int x_gate,
+                                                             int n) {
+    const int b = blockIdx.x;
+    const float* gate = (x_gate ? hx : hy) + (size_t)b * HD;
+    const float* val = (x_gate ? hy : hx) + (size_t)b * HD;
+    float* dgate = (x_gate ? dhx : dhy) + (size_t)b * HD;
+    float* dval = (x_gate ? dhy : dhx) + (size_t)b * HD;
+    for (int j = threadIdx.x; j < HD; j += 256) {
+        float dm = 0.f;
+        for (int c = 0; c < n; ++c) dm += g_out[(size_t)b * n + c] * Wo[(size_t)c * HD + j];
+        const float s = sigmoidf_(gate[j]);
+        dval[j] = dm * s;
+        dgate[j] = dm * val[j] * (s * (1.f - s));
+    }
+}
+// ws: 2 * B * 512 floats (d hx, d hy).  dx/dy, dW1/db1/dW2/db2, dWo/dbo are optional groups.
+int head_gated_joint_bwd(const float* x, const float* y, const float* hx, const float* hy, const float* W1, const float* W2,
+                         const float* Wo, const float* g_out, int x_gate, float* dx, float* dy, float* dW1, float* db1,
+                         float* dW2, float* db2, float* dWo, float* dbo, float* ws, int B, int n, hipStream_t st) {
+    float *dhx = ws, *dhy = ws + (size_t)B * HD;
+    if ((dx && dy) || dW1) {
+        hipLaunchKernelGGL(gated_joint_dh_kernel, dim3(B), dim3(256), 0, st, hx, hy, Wo, g_out, dhx, dhy, x_gate, n);
+        GDL_CHECK_LAUNCH("gated_joint_dh_kernel");
+    }
+    if (dx && dy) {
+        hipLaunchKernelGGL(gated_dx_kernel, dim3(B, 2), dim3(256), 0, st, dhx, dhy, W1, W2, dx, dy);
+        GDL_CHECK_LAUNCH("gated_dx_kernel");
+    }
+    if (dW1) {
+        hipLaunchKernelGGL(gated_dw1_kernel, dim3(HD, 2), dim3(256), 0, st, dhx, dhy, x, y, dW1, db1, dW2, db2, B);
+        GDL_CHECK_LAUNCH("gated_dw1_kernel");
+    }
+    if (dWo && dbo) {
+        // dWo[c][j] = sum_b g_out[b][c] * sigmoid(gate[b][j]) * value[b][j]: gated_dwo_kernel's `out` term with (gate, value) in
+        // the places of (hx, hy)
+        hipLaunchKernelGGL(gated_dwo_kernel, dim3(n), dim3(256), 0, st, x_gate ? hx : hy, x_gate ? hy : hx, (const float*)nullptr,
+                           (const float*)nullptr, g_out, 0, dWo, dbo, B, n);
+        GDL_CHECK_LAUNCH("gated_dwo_kernel");
+    }
+    return GDL_OK;
+}
+
 // valid() of /root/reference/main_dgl.py:206-219 without its per-sample host loop: for every sample the
 // arg-max of the three logit sets (softmax is monotone, np.argmax takes the first maximum) is compared with
 // the label and four per-class counters are bumped: num[label]++, acc*[label] += (argmax == label).

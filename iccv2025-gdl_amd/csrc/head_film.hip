@@ -317,4 +317,165 @@ int head_film_bwd(const float* x, const float* y, const float* Wfc, const float*
     return GDL_OK;
 }
 
+// ---------------------------------------------------------------- FiLM, trained jointly (fusion_modules.py:91-124)
+//   out = fc_out(fc(flatten(x (x) y))):  h_f[b][k] = x_b^T W_k y_b + bias_k  -- the fused form alone, nothing detached.
+// T[(k,i)][b] = (W_k y_b)[i] is needed for the y columns only: Bj = B rounded up to 64 columns (the GEMMs' channel granule)
+// against the DGL head's 2 * Bp -- half the f32 contraction over fc.weight at B = 64.  The workspace is the DGL head's
+// (gdl_head_film_workspace_bytes), laid out by film_layout; the pieces are used with Bj columns:
+//   V  [Bj][512] = y (padding rows zero)        T  [(k,i)][Bj]
+//   dh [3][B][512], only the fused plane [1] carries values (film_p_kernel / film_dbfc_kernel index it that way)
+//   U  [(k,i)][Bj] = dh[b][k] x_b[i]            out2 [Bj][512] = U^T A = dy
+//   P  the weight-gradient GEMM's operand (Bp columns, as in the DGL head) -- and before it is written, the split
+//      partials of the dy contraction (at most 27 MB of its >= 100 MB)
+static inline int film_bj(int B) { return (B + 63) / 64 * 64; }
+
+__global__ void film_vy_kernel(const float* __restrict__ y, float* __restrict__ V, int B) {
+    const int r = blockIdx.x;  // 0 .. Bj-1
+    for (int i = threadIdx.x; i < FD; i += blockDim.x) V[(size_t)r * FD + i] = r < B ? y[(size_t)r * FD + i] : 0.f;
+}
+// h_f[b][k] = bias[k] + sum_i x_b[i] T[(k,i)][b]     grid = (512 k, ceil(B / 64)); film_h_kernel's fused form: the same four
+// slices of i, the same order of the partial sums
+__global__ __launch_bounds__(256) void film_hf_kernel(const float* __restrict__ T, const float* __restrict__ x,
+                                                      const float* __restrict__ bias, float* __restrict__ hf, int B, int ld) {
+    __shared__ float red[4][64];
+    const int k = blockIdx.x;
+    const int bl = threadIdx.x & 63, b = blockIdx.y * 64 + bl, part = threadIdx.x >> 6;
+    float s = 0.f;
+    if (b < B) {
+        const float* Tk = T + (size_t)k * FD * ld + b;
+        for (int i = part; i < FD; i += 4) s += x[(size_t)b * FD + i] * Tk[(size_t)i * ld];
+    }
+    red[part][bl] = s;
+    __syncthreads();
+    if (part == 0 && b < B) hf[(size_t)b * FD + k] = ((red[0][bl] + red[1][bl]) + red[2][bl]) + red[3][bl] + bias[k];
+}
+// out[b][j] = bo[j] + sum_k Wo[j][k] h_f[b][k]      grid = B; film_out_kernel's fused logit set
+__global__ __launch_bounds__(256) void film_joint_out_kernel(const float* __restrict__ hf, const float* __restrict__ Wo,
+                                                             const float* __restrict__ bo, float* __restrict__ out, int n) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = hf[(size_t)b * FD + lane + 64 * i];
+    for (int j = wave; j < n; j += 4) {
+        const float* w = Wo + (size_t)j * FD;
+        float pf = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float wv = w[lane + 64 * i];
+            pf += wv * f[i];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pf += __shfl_xor(pf, o);
+        if (lane == 0) out[(size_t)b * n + j] = pf + bo[j];
+    }
+}
+// U[(k,i)][b] = dh_f[b][k] * x_b[i], padding columns zero.  One thread per (row, 4 columns)
+__global__ __launch_bounds__(256) void film_uj_kernel(const float* __restrict__ dhf, const float* __restrict__ x,
+                                                      float* __restrict__ U, int B, int ld) {
+    const int c4 = ld / 4;
+    const size_t total = (size_t)FROWS * c4;
+    for (size_t t = blockIdx.x * (size_t)256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const int q = (int)(t % c4);
+        const size_t row = t / c4;
+        const int k = (int)(row / FD), i = (int)(row % FD);
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int b = q * 4 + e;
+            v[e] = b < B ? dhf[(size_t)b * FD + k] * x[(size_t)b * FD + i] : 0.f;
+        }
+        *(float4*)(U + row * ld + q * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+// dx[b][i] = sum_k dh_f[b][k] T[(k,i)][b]  (T is still in the workspace: no GEMM);  dy[b][i] = out2[b][i]
+// grid = (512 i, ceil(B / 64)): a lane per sample (coalesced rows of T), four slices of k summed in a fixed order
+__global__ __launch_bounds__(256) void film_joint_dxy_kernel(const float* __restrict__ T, const float* __restrict__ dhf,
+                                                             const float* __restrict__ out2, float* __restrict__ dx,
+                                                             float* __restrict__ dy, int B, int ld) {
+    __shared__ float red[4][64];
+    const int i = blockIdx.x;
+    const int bl = threadIdx.x & 63, b = blockIdx.y * 64 + bl, part = threadIdx.x >> 6;
+    float s = 0.f;
+    if (b < B) {
+        const float* Ti = T + (size_t)i * ld + b;
+        for (int k = part; k < FD; k += 4) s += dhf[(size_t)b * FD + k] * Ti[(size_t)k * FD * ld];
+    }
+    red[part][bl] = s;
+    __syncthreads();
+    if (part == 0 && b < B) {
+        dx[(size_t)b * FD + i] = ((red[0][bl] + red[1][bl]) + red[2][bl]) + red[3][bl];
+        dy[(size_t)b * FD + i] = out2[(size_t)b * FD + i];
+    }
+}
+
+// hidden: [B][512] = h_f (kept by the caller for the backward, together with ws: T is reused)
+int head_film_joint_fwd(const float* x, const float* y, const float* Wfc, const float* bfc, const float* Wo, const float* bo,
+                        float* hidden, float* out, int B, int n, void* ws, size_t ws_bytes, hipStream_t st) {
+    GDL_REQUIRE(B >= 1 && B <= FILM_MAX_B, "head_film: B=%d (1..%d per call)", B, FILM_MAX_B);
+    const FilmWs w = film_layout((unsigned char*)ws, B);
+    if (!ws || ws_bytes < w.total) {
+        set_error("head_film_joint_fwd: workspace %zu < %zu bytes", ws_bytes, w.total);
+        return GDL_ERR_WORKSPACE;
+    }
+    const int Bj = film_bj(B);  // <= 2 * Bp: V, T, U and out2 of the DGL layout hold the Bj-column forms
+    hipLaunchKernelGGL(film_vy_kernel, dim3(Bj), dim3(256), 0, st, y, w.V, B);
+    GDL_CHECK_LAUNCH("film_vy_kernel");
+    int rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, (GatherEntry*)w.tab_a, st);
+    if (rc) return rc;
+    // T[(k,i)][b] = sum_j A[(k,i)][j] y_b[j]
+    rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(film_hf_kernel, dim3(FD, (B + 63) / 64), dim3(256), 0, st, w.T, x, bfc, hidden, B, Bj);
+    GDL_CHECK_LAUNCH("film_hf_kernel");
+    hipLaunchKernelGGL(film_joint_out_kernel, dim3(B), dim3(256), 0, st, hidden, Wo, bo, out, n);
+    GDL_CHECK_LAUNCH("film_joint_out_kernel");
+    return GDL_OK;
+}
+
+// Needs the workspace of the matching joint forward untouched (T, the gather table).  dx/dy, dWfc/dbfc, dWo/dbo: optional pairs.
+int head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const float* Wo, const float* hidden, const float* g_out,
+                        float* dx, float* dy, float* dWfc, float* dbfc, float* dWo, float* dbo, int B, int n, void* ws,
+                        size_t ws_bytes, hipStream_t st) {
+    GDL_REQUIRE(B >= 1 && B <= FILM_MAX_B, "head_film: B=%d (1..%d per call)", B, FILM_MAX_B);
+    const FilmWs w = film_layout((unsigned char*)ws, B);
+    if (!ws || ws_bytes < w.total) {
+        set_error("head_film_joint_bwd: workspace %zu < %zu bytes", ws_bytes, w.total);
+        return GDL_ERR_WORKSPACE;
+    }
+    const int Bp = film_bp(B), Bj = film_bj(B);
+    const float* dhf = w.dh + (size_t)B * FD;
+    // dh[1] = g_out Wo (the planes of the absent unimodal logit sets are written as zeros)
+    hipLaunchKernelGGL(film_dh_kernel, dim3(B, 3), dim3(256), 0, st, (const float*)nullptr, g_out, (const float*)nullptr, Wo, w.dh, B, n);
+    GDL_CHECK_LAUNCH("film_dh_kernel");
+    if (dWo && dbo) {
+        hipLaunchKernelGGL(film_dwo_kernel, dim3(n), dim3(256), 0, st, hidden, hidden, hidden, (const float*)nullptr, g_out,
+                           (const float*)nullptr, 0, dWo, dbo, B, n);
+        GDL_CHECK_LAUNCH("film_dwo_kernel");
+    }
+    int rc;
+    if (dx && dy) {
+        hipLaunchKernelGGL(film_uj_kernel, dim3(4096), dim3(256), 0, st, dhf, x, w.U, B, Bj);
+        GDL_CHECK_LAUNCH("film_uj_kernel");
+        // out2[b][j] = sum_(k,i) U[(k,i)][b] A[(k,i)][j]; the split partials go to the (not yet written) P piece
+        rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, FD, w.P, (size_t)FROWS * 3 * Bp * 4, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(film_joint_dxy_kernel, dim3(FD, (B + 63) / 64), dim3(256), 0, st, w.T, dhf, w.out2, dx, dy, B, Bj);
+        GDL_CHECK_LAUNCH("film_joint_dxy_kernel");
+    }
+    if (dWfc && dbfc) {  // the DGL head's phase-2 path: one block of Bp columns, P = dh_f (x) x, Z = y
+        hipLaunchKernelGGL(film_p_kernel, dim3(4096), dim3(256), 0, st, w.dh, x, y, w.P, B, Bp, 1);
+        GDL_CHECK_LAUNCH("film_p_kernel");
+        hipLaunchKernelGGL(film_z_kernel, dim3(FD), dim3(128), 0, st, x, y, w.Z, B, Bp, 1);
+        GDL_CHECK_LAUNCH("film_z_kernel");
+        rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, Bp, FD, 1, 1, 1, 0, (GatherEntry*)w.tab_p, st);
+        if (rc) return rc;
+        rc = conv_fwd(GDL_F32, w.P, w.Z, dWfc, nullptr, w.tab_p, 1, FROWS, 1, Bp, FD, 1, 1, 1, 0, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(film_dbfc_kernel, dim3(2), dim3(256), 0, st, w.dh, 0, dbfc, B);
+        GDL_CHECK_LAUNCH("film_dbfc_kernel");
+    }
+    return GDL_OK;
+}
+
+
 }  // namespace gdl

@@ -185,6 +185,18 @@ int head_film_fwd(const float* x, const float* y, const float* Wfc, const float*
 int head_film_bwd(const float* x, const float* y, const float* Wfc, const float* Wo, const float* hidden,
                   const float* g_x_out, const float* g_y_out, const float* g_out, int uni, float* dx, float* dy, float* dWfc,
                   float* dbfc, float* dWo, float* dbo, int B, int n, void* ws, size_t ws_bytes, hipStream_t st);
+// the jointly trained heads (GatedFusion with either gate, FiLM's fused form alone): one loss on `out`, nothing detached
+int head_gated_joint_fwd(const float* x, const float* y, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* Wo, const float* bo, float* hx, float* hy, float* out, int x_gate, int B, int n,
+                         hipStream_t st);
+int head_gated_joint_bwd(const float* x, const float* y, const float* hx, const float* hy, const float* W1, const float* W2,
+                         const float* Wo, const float* g_out, int x_gate, float* dx, float* dy, float* dW1, float* db1,
+                         float* dW2, float* db2, float* dWo, float* dbo, float* ws, int B, int n, hipStream_t st);
+int head_film_joint_fwd(const float* x, const float* y, const float* Wfc, const float* bfc, const float* Wo, const float* bo,
+                        float* hidden, float* out, int B, int n, void* ws, size_t ws_bytes, hipStream_t st);
+int head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const float* Wo, const float* hidden, const float* g_out,
+                        float* dx, float* dy, float* dWfc, float* dbfc, float* dWo, float* dbo, int B, int n, void* ws,
+                        size_t ws_bytes, hipStream_t st);
 // input.hip
 int logspec_frames(int L, int hop);
 int logspec(const float* wave, int B, int L, int n_fft, int hop, int reflect, float* out, hipStream_t st);

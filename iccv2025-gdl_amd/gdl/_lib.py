@@ -111,6 +111,10 @@ SIGNATURES = {
     "gdl_head_film_workspace_bytes": ("z", "i"),
     "gdl_head_film_fwd": ("i", "p" * 10 + "ii" + "pz" + "p"),
     "gdl_head_film_bwd": ("i", "p" * 8 + "i" + "p" * 6 + "ii" + "pz" + "p"),
+    "gdl_head_gated_joint_fwd": ("i", "p" * 11 + "iii" + "p"),
+    "gdl_head_gated_joint_bwd": ("i", "p" * 8 + "i" + "p" * 9 + "ii" + "p"),
+    "gdl_head_film_joint_fwd": ("i", "p" * 8 + "ii" + "pz" + "p"),
+    "gdl_head_film_joint_bwd": ("i", "p" * 12 + "ii" + "pz" + "p"),
     "gdl_logspec_frames": ("i", "ii"),
     "gdl_logspec": ("i", "p" + "iiiii" + "pp"),
     "gdl_frames_normalize": ("i", "p" + "lii" + "ppp" + "p"),

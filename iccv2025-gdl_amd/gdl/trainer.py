@@ -10,7 +10,8 @@ junction form below):
   then on A: fused grad statistics (total norm -> clip coefficient, per-encoder sum mean|g|)  (main_dgl.py:129-143)
              fused clip + SGD(momentum, weight decay) over the flat parameter arena            (:154)
              (or AdamW / Adagrad: `optimizer`, the script's --optimizer switch, :248-259)
-Junction form (other heads, the non-DGL step, and -- until a multi-GPU run has validated the early form's collective order --
+Junction form (other heads, the joint step -- mode="joint": ONE cross-entropy on the fused logits whose gradient flows through
+the head into both encoders, BASELINE config 1, for all four heads -- and -- until a multi-GPU run has validated the early form's collective order --
 every data-parallel run):
   audio encoder forward  (stream A)  ||  visual encoder forward (stream V)
   fusion head forward, 3x cross-entropy, head backward with the DGL truncation   (stream A)
@@ -127,20 +128,22 @@ class DGLTrainer:
             self.early_backward = False  # tuning aid (A/B)
         self.dtype = dtype if dtype is not None else model.audio_net.gdl_dtype
         head = model.fusion_module
-        # head kind: concat (fc_out [n,1024]; ConcatFusion / ConcatFusion_DGL) or sum (fc_x, fc_y [n,512]; SumFusion_DGL)
-        # or gated (fc_x, fc_y [512,512] + fc_out [n,512]; GatedFusion_DGL -- the step never gives fc_x / fc_y a
+        # head kind: concat (fc_out [n,1024]; ConcatFusion / ConcatFusion_DGL) or sum (fc_x, fc_y [n,512]; SumFusion(_DGL))
+        # or gated (fc_x, fc_y [512,512] + fc_out [n,512]; GatedFusion_DGL -- the DGL step never gives fc_x / fc_y a
         # gradient (main_dgl.py:114-122 drops phase 1's, loss_f sees detached hidden vectors), so like fc_auxi they stay
-        # outside the optimised arena)
-        # or film (fc [512, 262144] + fc_out [n,512]; FiLM_DGL: all four tensors are trained by loss_f)
+        # outside the optimised arena; GatedFusion in the joint step trains all six)
+        # or film (fc [512, 262144] + fc_out [n,512]; FiLM(_DGL): all four tensors are trained by the fused loss)
         self.head = ("gated" if hasattr(head, "fc_out") else "sum") if hasattr(head, "fc_x") else \
             ("film" if hasattr(head, "fc") else "concat")
         first = head.fc_x if self.head == "sum" else head.fc_out
         self.device = first.weight.device
         if self.device.type != "cuda":
             raise L.GdlError("DGLTrainer: the model must live on an MI355X (cuda) device; there is no CPU path")
-        if self.head != "concat" and mode != "dgl":
-            raise L.GdlError("DGLTrainer: the sum / gated / film heads are built for the DGL step only")
-        if self.head == "gated" and not getattr(head, "x_gate", True):
+        # mode: "dgl" = the step of main_dgl.py; "joint" (or its older name "concat") = the single-loss step of the jointly
+        # trained model (main.py:161-175): every head tensor and both encoders learn from CE(out) alone
+        self.joint = mode != "dgl"
+        self.x_gate = bool(getattr(head, "x_gate", True))
+        if self.head == "gated" and not self.x_gate and not self.joint:
             raise L.GdlError("DGLTrainer: GatedFusion_DGL is built for x_gate=True (basic_model.py:38)")
         self.n_classes = (head.fc_out if self.head == "gated" else first).weight.shape[0]
         # ---- flat arenas: [trained fusion-head tensors | audio_net (60) | visual_net (60)]
@@ -148,9 +151,11 @@ class DGLTrainer:
         if self.head == "film":
             named = [("fusion_module.fc.weight", head.fc.weight), ("fusion_module.fc.bias", head.fc.bias),
                      ("fusion_module.fc_out.weight", head.fc_out.weight), ("fusion_module.fc_out.bias", head.fc_out.bias)]
-        elif self.head == "sum":
+        elif self.head == "sum" or (self.head == "gated" and self.joint):
             named = [("fusion_module.fc_x.weight", head.fc_x.weight), ("fusion_module.fc_x.bias", head.fc_x.bias),
                      ("fusion_module.fc_y.weight", head.fc_y.weight), ("fusion_module.fc_y.bias", head.fc_y.bias)]
+            if self.head == "gated":  # the joint loss trains all six tensors (named_parameters() order)
+                named += [("fusion_module.fc_out.weight", head.fc_out.weight), ("fusion_module.fc_out.bias", head.fc_out.bias)]
         else:
             named = [("fusion_module.fc_out.weight", head.fc_out.weight), ("fusion_module.fc_out.bias", head.fc_out.bias)]
         nf = self.nf = len(named)
@@ -346,7 +351,7 @@ class DGLTrainer:
         if self.head == "film":
             if B > 512:
                 raise L.GdlError("DGLTrainer: the FiLM head handles at most 512 samples per step")
-            self.hidden = torch.empty((3, B, 512), device=d)
+            self.hidden = torch.empty((B, 512) if self.joint else (3, B, 512), device=d)  # joint: h_f alone
             self.head_ws = torch.empty(self.lib.gdl_head_film_workspace_bytes(B), dtype=torch.uint8, device=d)
         if self.head == "gated":  # hidden vectors (saved for the backward) + its scratch
             self.hx, self.hy = torch.empty((B, 512), device=d), torch.empty((B, 512), device=d)
@@ -515,9 +520,12 @@ class DGLTrainer:
                 L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.pviews[0]), L.ptr(self.g_a),
                        L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(self.dfa), L.ptr(self.dfv), L.ptr(self.gviews[0]),
                        L.ptr(self.gviews[1]), B, n, st)
-        else:  # BASELINE config 1: ConcatFusion + one CE loss (main.py:161-175)
-            L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.pviews[0]), None, None, L.ptr(self.g_f),
-                   1, 0, L.ptr(self.dfa), L.ptr(self.dfv), L.ptr(self.gviews[0]), L.ptr(self.gviews[1]), B, n, st)
+        else:  # BASELINE config 1: one CE loss (main.py:161-175) through the head into both encoders
+            # Only the feature gradients stand between the head and the encoder backwards.  Without a process group the head's
+            # parameter gradients follow behind the junction event, on this stream (= the audio chain, the shorter one) in front
+            # of the audio backward; the visual chain, the critical path, starts as soon as dfa / dfv exist.  Same kernels, same
+            # numbers.  With a process group the fusion bucket's collective is launched at the junction: everything first.
+            self._joint_head_backward(st, True, self.reducer is not None)
         self._mark(main, "head_done")
         red = self.reducer
         if red is not None:
@@ -525,6 +533,8 @@ class DGLTrainer:
         ev2 = main.record_event()
         self.s_a.wait_event(ev2)
         self.s_v.wait_event(ev2)
+        if not dgl and red is None:
+            self._joint_head_backward(st, False, True)
         gv, ga = self.gviews[nf + 60:nf + 60 + self.nv], self.gviews[nf:nf + 60]
         if red is None:
             with torch.cuda.stream(self.s_v):
@@ -577,11 +587,37 @@ class DGLTrainer:
             self.stats_log_pos += 1
         self.steps += 1
 
+    def _joint_head_backward(self, st, feat, par):
+        """The joint step's head backward from self.g_f: `feat` -- dfa / dfv; `par` -- the gradients of every head tensor."""
+        pv, B, n = self.pviews, self.B, self.n_classes
+        dfa, dfv = (L.ptr(self.dfa), L.ptr(self.dfv)) if feat else (None, None)
+        gv = [L.ptr(g) if par else None for g in self.gviews[:self.nf]]
+        if self.head == "film":  # fusion_modules.py:91-124
+            L.call("gdl_head_film_joint_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.hidden),
+                   L.ptr(self.g_f), dfa, dfv, gv[0], gv[1], gv[2], gv[3], B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
+        elif self.head == "gated":  # fusion_modules.py:181-210
+            L.call("gdl_head_gated_joint_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.hx), L.ptr(self.hy), L.ptr(pv[0]),
+                   L.ptr(pv[2]), L.ptr(pv[4]), L.ptr(self.g_f), int(self.x_gate), dfa, dfv, gv[0], gv[1], gv[2], gv[3], gv[4],
+                   gv[5], L.ptr(self.head_ws), B, n, st)
+        elif self.head == "sum":  # fusion_modules.py:5-13
+            L.call("gdl_head_sum_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), None, None, L.ptr(self.g_f),
+                   1, 0, dfa, dfv, gv[0], gv[1], gv[2], gv[3], B, n, st)
+        else:  # fusion_modules.py:33-42
+            L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), None, None, L.ptr(self.g_f), 1, 0,
+                   dfa, dfv, gv[0], gv[1], B, n, st)
+
     def _head_forward(self, dgl, st):
         """(out, out_a, out_v) from the pooled features self.fa / self.fv."""
         pv, B, n = self.pviews, self.B, self.n_classes
         oa, ov = (L.ptr(self.out_a), L.ptr(self.out_v)) if dgl else (None, None)
-        if self.head == "film":  # fusion_modules.py:140-178
+        if self.head == "film" and self.joint:  # fusion_modules.py:105-124: the fused form alone
+            L.call("gdl_head_film_joint_fwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[1]), L.ptr(pv[2]),
+                   L.ptr(pv[3]), L.ptr(self.hidden), L.ptr(self.out), B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
+        elif self.head == "gated" and self.joint:  # fusion_modules.py:198-210 (all six tensors live in the arena)
+            L.call("gdl_head_gated_joint_fwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[1]), L.ptr(pv[2]),
+                   L.ptr(pv[3]), L.ptr(pv[4]), L.ptr(pv[5]), L.ptr(self.hx), L.ptr(self.hy), L.ptr(self.out), int(self.x_gate),
+                   B, n, st)
+        elif self.head == "film":  # fusion_modules.py:140-178
             L.call("gdl_head_film_fwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[1]), L.ptr(pv[2]), L.ptr(pv[3]),
                    L.ptr(self.hidden), L.ptr(self.out), oa, ov, B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
         elif self.head == "gated":  # fusion_modules.py:232-250

@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from .backbone import resnet18
-from .fusion_modules import ConcatFusion, ConcatFusion_DGL, FiLM_DGL, GatedFusion_DGL, SumFusion_DGL  # noqa: F401
+from .fusion_modules import (ConcatFusion, ConcatFusion_DGL, FiLM, FiLM_DGL, GatedFusion, GatedFusion_DGL,  # noqa: F401
+                             SumFusion, SumFusion_DGL)
 
 N_CLASSES = {'VGGSound': 309, 'KineticSound': 34, 'kinect400': 400, 'CREMAD': 6, 'AVE': 28}  # basic_model.py:15-26
 
@@ -92,18 +93,28 @@ class AVClassifier_DGL_Swin(nn.Module):
 
 
 class AVClassifier(nn.Module):
-    """BASELINE config 1: the non-DGL concat model of main.py.  The reference class of this name
+    """BASELINE config 1: the jointly trained (non-DGL) model of main.py.  The reference class of this name
     no longer exists in models/basic_model.py (main.py:19 cannot be imported); this
     restates its math from the parts that do exist: the two encoders, the pooling glue of
-    basic_model.py:73-82 and `ConcatFusion` (fusion_modules.py:33-42).  Returns (a, v, out)."""
+    basic_model.py:73-82 and the joint fusion heads `ConcatFusion` (fusion_modules.py:33-42), `SumFusion` (:5-13),
+    `GatedFusion(x_gate=True)` (:181-210) and `FiLM(dim=512)` (:91-124), chosen by args.fusion_method as
+    AVClassifier_DGL chooses their DGL twins.  Returns the head's tuple (a, v, out)."""
 
     def __init__(self, args):
         super(AVClassifier, self).__init__()
         if args.dataset not in N_CLASSES:
             raise NotImplementedError('Incorrect dataset name {}'.format(args.dataset))
-        if args.fusion_method != 'concat':
-            raise NotImplementedError('gdl: fusion method {!r} is not built yet (concat only)'.format(args.fusion_method))
-        self.fusion_module = ConcatFusion(output_dim=N_CLASSES[args.dataset])
+        fusion, n_classes = args.fusion_method, N_CLASSES[args.dataset]
+        if fusion == 'sum':
+            self.fusion_module = SumFusion(output_dim=n_classes)
+        elif fusion == 'concat':
+            self.fusion_module = ConcatFusion(output_dim=n_classes)
+        elif fusion == 'gated':
+            self.fusion_module = GatedFusion(output_dim=n_classes, x_gate=True)
+        elif fusion == 'film':
+            self.fusion_module = FiLM(dim=512, output_dim=n_classes, x_film=True)
+        else:
+            raise NotImplementedError('Incorrect fusion method: {}!'.format(fusion))
         self.audio_net = resnet18(modality='audio', args=args)
         self.visual_net = resnet18(modality='visual', args=args)
         self.modality = 'full'

@@ -306,6 +306,24 @@ GDL_API int gdl_head_film_bwd(const float* x, const float* y, const float* Wfc, 
                               const float* g_x_out, const float* g_y_out, const float* g_out, int uni_in_dw, float* dx,
                               float* dy, float* dWfc, float* dbfc, float* dWo, float* dbo, int B, int n_classes, void* ws,
                               size_t ws_bytes, void* stream);
+/* FiLM trained jointly (fusion_modules.py:91-124 at dim = 512; BASELINE config 1 with the FiLM head): nothing is detached and
+ * only the fused form exists,
+ *   h_f[b][k] = sum_ij x_b[i] y_b[j] W[k,i,j] + bias_k,   out = fc_out(h_f)        (replaces :116-122: two unsqueezes, bmm,
+ *   view, two Linears).
+ * T[(k,i)][b] = (W_k y_b)[i] is computed for the y columns only (B rounded up to 64 columns, against 2 * roundup(B, 32) of
+ * gdl_head_film_fwd: half the f32 contraction over fc.weight at B = 64).  Backward from g_out [B][n] (autograd of the above):
+ *   dh = g_out Wo;   dx[b][i] = sum_k dh[b][k] T[(k,i)][b]  (no GEMM: T is still in the workspace);
+ *   dy[b][j] = sum_(k,i) dh[b][k] x_b[i] W[k,i,j]  (one weight-gradient contraction over fc.weight);
+ *   dWfc[k,i,j] = sum_b dh[b][k] x_b[i] y_b[j], dbfc = sum_b dh;  dWo = g_out^T h_f, dbo = sum_b g_out.
+ * hidden: [B][512] float32 (h_f alone -- NOT gdl_head_film_fwd's [3][B][512]), produced by joint_fwd and consumed, with the
+ * SAME untouched workspace, by joint_bwd.  Workspace: gdl_head_film_workspace_bytes(B); B <= 512 and the error codes as for
+ * gdl_head_film_fwd / _bwd.  dx/dy, dWfc/dbfc, dWo/dbo are optional pairs.  `out` is bit-identical to gdl_head_film_fwd's. */
+GDL_API int gdl_head_film_joint_fwd(const float* x, const float* y, const float* Wfc, const float* bfc, const float* Wo,
+                                    const float* bo, float* hidden, float* out, int B, int n_classes, void* ws,
+                                    size_t ws_bytes, void* stream);
+GDL_API int gdl_head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const float* Wo, const float* hidden,
+                                    const float* g_out, float* dx, float* dy, float* dWfc, float* dbfc, float* dWo, float* dbo,
+                                    int B, int n_classes, void* ws, size_t ws_bytes, void* stream);
 /* GatedFusion_DGL (fusion_modules.py:213-250, x_gate = True; SURVEY next row N2): fc_x, fc_y: Linear(512, 512),
  * fc_out: Linear(512, n).  hx = fc_x(x), hy = fc_y(y) ([B][512], returned: saved for the backward);
  *   out = fc_out(sigmoid(hx.detach()) * hy.detach()),  x_out = fc_out(sigmoid(hx) * hx),  y_out = fc_out(sigmoid(hy) * hy).
@@ -319,10 +337,28 @@ GDL_API int gdl_head_gated_bwd(const float* x, const float* y, const float* hx, 
                                const float* W2, const float* Wo, const float* g_x_out, const float* g_y_out,
                                const float* g_out, int uni_in_dw, float* dx, float* dy, float* dW1, float* db1, float* dW2,
                                float* db2, float* dWo, float* dbo, float* ws, int B, int n_classes, void* stream);
+/* GatedFusion trained jointly (fusion_modules.py:181-210; BASELINE config 1 with the gated head): hx = fc_x(x), hy = fc_y(y),
+ *   x_gate != 0: out = fc_out(sigmoid(hx) * hy)          (:203-205)
+ *   x_gate == 0: out = fc_out(hx * sigmoid(hy))          (:206-208)
+ * hx, hy [B][512] are returned (saved for the backward).  With x_gate != 0 `out` is bit-identical to gdl_head_gated_fwd's.
+ * Backward from g_out [B][n], autograd of the above (gate = hx, value = hy if x_gate, else swapped; s = sigmoid(gate)):
+ *   dm = g_out Wo;   d(value) = dm * s;   d(gate) = dm * value * s (1 - s);
+ *   dx = dhx W1, dy = dhy W2;   dW1 = dhx^T x, db1 = sum_b dhx;   dW2 = dhy^T y, db2 = sum_b dhy;
+ *   dWo = g_out^T (s * value), dbo = sum_b g_out.
+ * dx/dy, dW1/db1/dW2/db2, dWo/dbo are optional groups.  ws: 2*B*512 floats. */
+GDL_API int gdl_head_gated_joint_fwd(const float* x, const float* y, const float* W1, const float* b1, const float* W2,
+                                     const float* b2, const float* Wo, const float* bo, float* hx, float* hy, float* out,
+                                     int x_gate, int B, int n_classes, void* stream);
+GDL_API int gdl_head_gated_joint_bwd(const float* x, const float* y, const float* hx, const float* hy, const float* W1,
+                                     const float* W2, const float* Wo, const float* g_out, int x_gate, float* dx, float* dy,
+                                     float* dW1, float* db1, float* dW2, float* db2, float* dWo, float* dbo, float* ws, int B,
+                                     int n_classes, void* stream);
 /* SumFusion_DGL (fusion_modules.py:16-30; SURVEY next row N2): fc_x, fc_y: Linear(512, n).
  *   x_out = fc_x(x), y_out = fc_y(y), out = fc_x(x.detach()) + fc_y(y.detach()).
  * Same flag meaning as the concat head; the sum head has two weight matrices [n][512] and two biases
- * (dbx = sum_b (g_out + uni*g_x_out), dby likewise). */
+ * (dbx = sum_b (g_out + uni*g_x_out), dby likewise).
+ * SumFusion trained jointly (fusion_modules.py:5-13: out = fc_x(x) + fc_y(y), one loss) is the same pair of calls:
+ * fwd with x_out = y_out = NULL, bwd with g_x_out = g_y_out = NULL, out_reaches_xy = 1, uni_in_dw = 0. */
 GDL_API int gdl_head_sum_fwd(const float* x, const float* y, const float* Wx, const float* bx, const float* Wy,
                              const float* by, float* out, float* x_out, float* y_out, int B, int n_classes, void* stream);
 GDL_API int gdl_head_sum_bwd(const float* x, const float* y, const float* Wx, const float* Wy, const float* g_x_out,
