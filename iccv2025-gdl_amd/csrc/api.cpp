@@ -265,6 +265,23 @@ int gdl_head_uni_dfeat_w(const float* f, const float* Wp, int ldw, const float* 
     GDL_REQUIRE(f && Wp && bp && labels && df && B > 0 && n_classes > 0 && ldw >= width, "head_uni_dfeat_w: bad arguments");
     return head_uni_dfeat(f, Wp, ldw, bp, labels, scale, df, B, n_classes, width, (hipStream_t)stream);
 }
+int gdl_head_cls_fwd(const float* f, const float* W, const float* b, float* out, int B, int n_classes, int width, void* stream) {
+    GDL_REQUIRE(f && W && b && out && B > 0 && n_classes > 0, "head_cls_fwd: bad arguments");
+    GDL_REQUIRE(width == 512, "head_cls_fwd: feature width %d (the classifier is built for 512)", width);
+    return head_cls_fwd(f, W, b, out, B, n_classes, (hipStream_t)stream);
+}
+int gdl_head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B, int n_classes,
+                     int width, void* stream) {
+    GDL_REQUIRE(f && W && g_out && B > 0 && n_classes > 0, "head_cls_bwd: bad arguments");
+    GDL_REQUIRE(width == 512, "head_cls_bwd: feature width %d (the classifier is built for 512)", width);
+    return head_cls_bwd(f, W, g_out, df, dW, db, B, n_classes, (hipStream_t)stream);
+}
+int gdl_head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out, float* loss,
+                    float* dlogits, float* df, int B, int n_classes, int width, void* stream) {
+    GDL_REQUIRE(f && W && b && labels && out && loss && dlogits && df && B > 0 && n_classes > 0, "head_cls_ce: bad arguments");
+    GDL_REQUIRE(width == 512, "head_cls_ce: feature width %d (the classifier is built for 512)", width);
+    return head_cls_ce(f, W, b, labels, scale, out, loss, dlogits, df, B, n_classes, (hipStream_t)stream);
+}
 int gdl_head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out,
                         float* y_out, int B, int n_classes, void* stream) {
     GDL_REQUIRE(x && y && W && b && out && B > 0 && n_classes > 0, "head_concat_fwd: bad arguments");

@@ -1,0 +1,281 @@
+// head_cls.hip -- the classifier of the unimodal baselines, float32.
+//
+// AVClassifier_DGL with modality 'audio' / 'visual' (the reference's models/basic_model.py:46-59, 88-122) puts one
+// nn.Linear(512, n_classes) on the pooled features of its only encoder; main.py trains it with one CrossEntropyLoss.
+//   out = f W^T + b;   loss = mean CE(out, labels);   dlogits = scale * (softmax(out) - onehot) / B
+//   df = dlogits W;    dW = dlogits^T f;    db = sum_b dlogits
+// Three entry points: the forward (eval, the drop-in module), the backward for an arbitrary upstream gradient (the drop-in
+// module; the step's parameter gradients with df = NULL), and head_cls_ce, the ONE launch that stands between the encoder's
+// forward and its backward in the training step (logits, loss, dlogits and df), where head_uni_dfeat_kernel stands in the
+// DGL step.  Sizes are tiny (B x 512 x n): latency bound, no MFMA.
+//
+// Every sum has ONE order, shared by the three launchers through the device functions below, so head_cls_ce's out, dlogits
+// and df carry the bits of head_cls_fwd + softmax_ce (head.hip) + head_cls_bwd:
+//   a logit      : lane l of a wave adds f[l + 64 i] * W[j][l + 64 i] for i = 0 .. 7 (fmaf chain), xor butterfly 32 .. 1, + b[j]
+//   softmax / CE : softmax_ce_block's -- max (exact in any order), expf(l - max) summed in class order, lse = max + logf(sum),
+//                  dlogits = scale * (expf(l - lse) - onehot) / B
+//   df[i]        : classes in ascending order (fmaf chain), eight weight loads in flight
+//   dW / db      : samples in ascending order
+#include <map>
+#include <mutex>
+#include <utility>
+
+#include "common.h"
+#include "ops.h"
+#include "prof.h"
+
+namespace gdl {
+
+constexpr int CLS_D = 512;   // feature width
+constexpr int CLS_ND = 8;    // features per lane
+constexpr int CLS_MAXN = 512;
+
+__device__ __forceinline__ void cls_load_feat(const float* __restrict__ f, int lane, float (&fv)[CLS_ND]) {
+#pragma unroll
+    for (int i = 0; i < CLS_ND; ++i) fv[i] = f[lane + 64 * i];
+}
+// the lane's share of two logits at a time (their loads and butterflies overlap); every lane returns the full sums
+__device__ __forceinline__ void cls_dot2(const float* __restrict__ w, const float* __restrict__ w2, const float (&fv)[CLS_ND], int lane,
+                                         float& pa, float& pb) {
+    pa = 0.f, pb = 0.f;
+#pragma unroll
+    for (int i = 0; i < CLS_ND; ++i) pa = fmaf(w[lane + 64 * i], fv[i], pa);
+#pragma unroll
+    for (int i = 0; i < CLS_ND; ++i) pb = fmaf(w2[lane + 64 * i], fv[i], pb);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        pa += __shfl_xor(pa, o);
+        pb += __shfl_xor(pb, o);
+    }
+}
+// df[i] = sum_j g[j] W[j][i], classes ascending; g in LDS
+__device__ __forceinline__ float cls_df_walk(const float* g, const float* __restrict__ W, int i, int n) {
+    const float* w = W + i;
+    float s = 0.f;
+    int j = 0;
+    for (; j + 8 <= n; j += 8) {
+        float q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) q[u] = w[(size_t)(j + u) * CLS_D];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s = fmaf(g[j + u], q[u], s);
+    }
+    for (; j < n; ++j) s = fmaf(g[j], w[(size_t)j * CLS_D], s);
+    return s;
+}
+
+// ---------------------------------------------------------------- forward
+// grid = (B, ceil(n / 8)): a block's four waves own eight classes of one sample, two per wave
+constexpr int CLS_FWD_CH = 8;
+__global__ __launch_bounds__(256) void head_cls_fwd_kernel(const float* __restrict__ f, const float* __restrict__ W,
+                                                           const float* __restrict__ bias, float* __restrict__ out, int n) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.y * CLS_FWD_CH + wave, j2 = j + 4;
+    if (j >= n) return;
+    float fv[CLS_ND];
+    cls_load_feat(f + (size_t)b * CLS_D, lane, fv);
+    float pa, pb;
+    cls_dot2(W + (size_t)j * CLS_D, W + (size_t)(j2 < n ? j2 : j) * CLS_D, fv, lane, pa, pb);
+    if (lane == 0) {
+        out[(size_t)b * n + j] = pa + bias[j];
+        if (j2 < n) out[(size_t)b * n + j2] = pb + bias[j2];
+    }
+}
+int head_cls_fwd(const float* f, const float* W, const float* b, float* out, int B, int n, hipStream_t st) {
+    GDL_REQUIRE(n <= CLS_MAXN, "head_cls_fwd: at most %d classes", CLS_MAXN);
+    hipLaunchKernelGGL(head_cls_fwd_kernel, dim3(B, ceil_div(n, CLS_FWD_CH)), dim3(256), 0, st, f, W, b, out, n);
+    GDL_CHECK_LAUNCH("head_cls_fwd_kernel");
+    return GDL_OK;
+}
+
+// ---------------------------------------------------------------- backward for an arbitrary upstream gradient
+// grid = (B, 2): a thread per feature, the sample's class gradients staged in LDS once
+__global__ __launch_bounds__(256) void head_cls_dfeat_kernel(const float* __restrict__ W, const float* __restrict__ g_out,
+                                                             float* __restrict__ df, int n) {
+    __shared__ float g[CLS_MAXN];
+    const int b = blockIdx.x;
+    for (int j = threadIdx.x; j < n; j += 256) g[j] = g_out[(size_t)b * n + j];
+    __syncthreads();
+    const int i = blockIdx.y * 256 + threadIdx.x;
+    df[(size_t)b * CLS_D + i] = cls_df_walk(g, W, i, n);
+}
+// grid = (n, 2): a thread per weight-gradient element; the batch's gradients of class j staged in LDS 256 samples at a time,
+// summed in sample order; db[j] = their plain sum in the same order (the y = 0 block)
+__global__ __launch_bounds__(256) void head_cls_dw_kernel(const float* __restrict__ f, const float* __restrict__ g_out,
+                                                          float* __restrict__ dW, float* __restrict__ db, int B, int n) {
+    __shared__ float gs[256];
+    const int j = blockIdx.x, i = blockIdx.y * 256 + threadIdx.x;
+    float s = 0.f, sb = 0.f;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int nb = min(256, B - b0);
+        __syncthreads();
+        if ((int)threadIdx.x < nb) gs[threadIdx.x] = g_out[(size_t)(b0 + threadIdx.x) * n + j];
+        __syncthreads();
+#pragma unroll 8
+        for (int b = 0; b < nb; ++b) {
+            s = fmaf(gs[b], f[(size_t)(b0 + b) * CLS_D + i], s);
+            sb += gs[b];
+        }
+    }
+    if (dW) dW[(size_t)j * CLS_D + i] = s;
+    if (db && blockIdx.y == 0 && threadIdx.x == 0) db[j] = sb;
+}
+static_assert(CLS_D == 2 * 256, "head_cls_dfeat_kernel / head_cls_dw_kernel: two blocks of 256 features");
+int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B, int n,
+                 hipStream_t st) {
+    GDL_REQUIRE(n <= CLS_MAXN, "head_cls_bwd: at most %d classes", CLS_MAXN);
+    if (df) {
+        hipLaunchKernelGGL(head_cls_dfeat_kernel, dim3(B, 2), dim3(256), 0, st, W, g_out, df, n);
+        GDL_CHECK_LAUNCH("head_cls_dfeat_kernel");
+    }
+    if (dW || db) {
+        // (db alone: the y = 0 blocks; they still walk the features of their half, B x 256 fmaf each -- never on a hot path)
+        hipLaunchKernelGGL(head_cls_dw_kernel, dim3(n, dW ? 2 : 1), dim3(256), 0, st, f, g_out, dW, db, B, n);
+        GDL_CHECK_LAUNCH("head_cls_dw_kernel");
+    }
+    return GDL_OK;
+}
+
+// ---------------------------------------------------------------- the training step's launch
+// grid = B, 16 waves per sample: head_uni_dfeat_kernel's schedule (head.hip: the classes go round the 16 waves two at a time,
+// max and exp by all threads, only the sum of the exponentials walked in class order by one thread, df an ascending walk per
+// feature by the first 512 threads) plus the three stores the unimodal step needs -- out, dlogits and the sample's loss term.
+//
+// The mean over the samples = over the blocks.  df occupies waves 0 .. 7 only; wave 15, idle by then, publishes the sample's
+// term (lse - logit[label]) and draws a ticket; the block whose ticket is the last sums all B terms in ONE order (lane l takes
+// b = l, l + 64, ..., then the xor butterfly 32 .. 1), writes loss[0] and zeroes the counter for the next launch.  No
+// floating-point atomic; the result does not depend on which block comes last.
+// Visibility between the blocks (per-XCD L2s are not coherent): the term is an agent-scope (write-through) store of the one
+// lane that also draws the ticket, waited for before the ticket's agent-scope acq_rel add; the reader's loads are agent-scope
+// loads issued after its add has returned.  `part` / `cnt` belong to the launching stream (ce_slot below): launches of one
+// stream are ordered, so the counter is 0 at every kernel start.
+__global__ __launch_bounds__(1024) void head_cls_ce_kernel(const float* __restrict__ f, const float* __restrict__ W,
+                                                          const float* __restrict__ bias, const int64_t* __restrict__ labels,
+                                                          float scale, float* __restrict__ out, float* __restrict__ loss,
+                                                          float* __restrict__ dlogits, float* __restrict__ df,
+                                                          float* __restrict__ part, unsigned* __restrict__ cnt, int B, int n) {
+    constexpr int NW = 16;
+    __shared__ float lg[CLS_MAXN], dl[CLS_MAXN], ex[CLS_MAXN];
+    __shared__ float wmx[NW];
+    __shared__ float lse_s;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float fv[CLS_ND];
+    cls_load_feat(f + (size_t)b * CLS_D, lane, fv);
+    for (int j = wave; j < n; j += 2 * NW) {
+        const int j2 = j + NW;
+        float pa, pb;
+        cls_dot2(W + (size_t)j * CLS_D, W + (size_t)(j2 < n ? j2 : j) * CLS_D, fv, lane, pa, pb);
+        if (lane == 0) {
+            lg[j] = pa + bias[j];
+            if (j2 < n) lg[j2] = pb + bias[j2];
+        }
+    }
+    __syncthreads();
+    {
+        float mx = -INFINITY;
+        for (int j = threadIdx.x; j < n; j += 1024) {
+            const float l = lg[j];
+            out[(size_t)b * n + j] = l;
+            mx = fmaxf(mx, l);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        if (lane == 0) wmx[wave] = mx;
+    }
+    __syncthreads();
+    float mx = wmx[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, wmx[w]);
+    for (int j = threadIdx.x; j < n; j += 1024) ex[j] = expf(lg[j] - mx);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float se = 0.f;
+        for (int j = 0; j < n; ++j) se += ex[j];
+        lse_s = mx + logf(se);
+    }
+    __syncthreads();
+    // a class index outside [0, n) (a device assert in the reference's CrossEntropyLoss): no one-hot term, NaN in the loss
+    const long lab64 = (long)labels[b];
+    const int lab = (lab64 >= 0 && lab64 < n) ? (int)lab64 : -1;
+    const float lse = lse_s;
+    for (int j = threadIdx.x; j < n; j += 1024) {
+        const float d = scale * (expf(lg[j] - lse) - (j == lab ? 1.f : 0.f)) / (float)B;
+        dl[j] = d;
+        dlogits[(size_t)b * n + j] = d;
+    }
+    __syncthreads();  // (the last barrier: from here on the waves part ways)
+    if (threadIdx.x < CLS_D) {
+        df[(size_t)b * CLS_D + threadIdx.x] = cls_df_walk(dl, W, threadIdx.x, n);
+    } else if (wave == NW - 1) {
+        int last = 0;
+        if (lane == 0) {
+            st_agent(part + b, lab >= 0 ? lse - lg[lab] : __builtin_nanf(""));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(B - 1);
+        }
+        last = __shfl(last, 0);
+        if (last) {
+            float s = 0.f;
+            for (int k = lane; k < B; k += 64) s += __hip_atomic_load(part + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            if (lane == 0) {
+                loss[0] = s / (float)B;
+                __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+// The ticket counter and the B loss terms of a launch in flight: device memory owned by the library, one slot per (device,
+// stream), made at the first call on that stream (the only time this launcher allocates, zeroes and thereby synchronises) and
+// grown when a larger batch comes.  Launches on one stream run one after the other, launches on different streams use
+// different slots: no two kernels in flight share a counter.
+namespace {
+struct CeSlot {
+    float* base = nullptr;  // [0]: the counter, on a 256-byte line of its own; [64 ..): the terms
+    int cap = 0;
+};
+std::mutex ce_mu;
+std::map<std::pair<int, hipStream_t>, CeSlot> ce_slots;
+}  // namespace
+static int ce_slot(hipStream_t st, int B, float** part, unsigned** cnt) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return check_hip(hipGetLastError(), "head_cls_ce: hipGetDevice");
+    std::lock_guard<std::mutex> lock(ce_mu);
+    CeSlot& s = ce_slots[{dev, st}];
+    if (s.cap < B) {
+        if (s.base) {
+            hipError_t e = hipFree(s.base);  // (waits for the device: the slot's last launch is done)
+            s.base = nullptr, s.cap = 0;
+            if (e != hipSuccess) return check_hip(e, "head_cls_ce: hipFree");
+        }
+        const int cap = (int)align_up((size_t)B, 1024);
+        float* p = nullptr;
+        hipError_t e = hipMalloc((void**)&p, (64 + (size_t)cap) * sizeof(float));
+        if (e != hipSuccess) return check_hip(e, "head_cls_ce: hipMalloc");
+        e = hipMemset(p, 0, (64 + (size_t)cap) * sizeof(float));
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return check_hip(e, "head_cls_ce: hipMemset");
+        }
+        s.base = p, s.cap = cap;
+    }
+    *cnt = (unsigned*)s.base;
+    *part = s.base + 64;
+    return GDL_OK;
+}
+int head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out, float* loss,
+                float* dlogits, float* df, int B, int n, hipStream_t st) {
+    GDL_REQUIRE(n <= CLS_MAXN, "head_cls_ce: at most %d classes", CLS_MAXN);
+    float* part = nullptr;
+    unsigned* cnt = nullptr;
+    const int rc = ce_slot(st, B, &part, &cnt);
+    if (rc != GDL_OK) return rc;
+    ProfScope prof("gdl::head_cls_ce_kernel", PROF_HBM, st, (double)B * CLS_D * 8.0 + (double)n * CLS_D * 4.0 + (double)B * n * 8.0);
+    hipLaunchKernelGGL(head_cls_ce_kernel, dim3(B), dim3(1024), 0, st, f, W, b, labels, scale, out, loss, dlogits, df, part, cnt, B, n);
+    GDL_CHECK_LAUNCH("head_cls_ce_kernel");
+    return GDL_OK;
+}
+
+}  // namespace gdl

@@ -161,6 +161,11 @@ int avgpool_bwd(int dtype, const float* dfeat, void* dx, int B, int T, int HW, i
 // head.hip
 int head_uni_dfeat(const float* f, const float* Wp, int ldw, const float* bp, const int64_t* labels, float scale, float* df, int B,
                    int n, int width, hipStream_t st);
+// head_cls.hip: the Linear(512, n) classifier of the unimodal baselines
+int head_cls_fwd(const float* f, const float* W, const float* b, float* out, int B, int n, hipStream_t st);
+int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B, int n, hipStream_t st);
+int head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out, float* loss,
+                float* dlogits, float* df, int B, int n, hipStream_t st);
 int head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out, float* y_out,
                     int B, int n, hipStream_t st);
 int head_concat_bwd(const float* x, const float* y, const float* W, const float* g_x_out, const float* g_y_out,

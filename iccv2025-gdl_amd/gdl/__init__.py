@@ -6,3 +6,16 @@ raises.
 """
 from . import _lib  # noqa: F401
 from ._lib import GdlError  # noqa: F401
+
+
+def __getattr__(name):
+    """`gdl.DGLTrainer` / `gdl.UnimodalTrainer`: the two runners, imported on first use (they import torch)."""
+    if name == "DGLTrainer":
+        from .trainer import DGLTrainer
+
+        return DGLTrainer
+    if name == "UnimodalTrainer":
+        from .unimodal import UnimodalTrainer
+
+        return UnimodalTrainer
+    raise AttributeError(f"module 'gdl' has no attribute {name!r}")

@@ -1,0 +1,216 @@
+"""Native training step of the unimodal baselines: the audio encoder alone or the visual encoder alone with a
+`Linear(512, n_classes)` classifier (the reference's models/basic_model.py:46-59, 88-122, `args.modality` 'audio' / 'visual'),
+trained by the body of its main.py -- one CrossEntropyLoss on `out`, backward, clip_grad_norm_(.., 40), the optimizer.
+
+Per step (all asynchronous, nothing is read back unless `read()` is called), on the process-wide chain streams of
+gdl.trainer (the modality's own as the chain, the other one -- idle here -- as the side lane):
+  chain: encoder forward -> gdl_head_cls_ce (logits, loss, dlogits, feature gradient: one launch) -> encoder backward
+         -> fused grad statistics -> fused clip + update
+  lane : the classifier's dW / db from the stored dlogits (gdl_head_cls_bwd, df = NULL) behind the start of the encoder
+         backward, then that backward's weight gradients (gdl_encoder_borrow_side_stream)
+The flat arena is [classifier.weight, classifier.bias | the encoder's 60 tensors] with the optimizer groups 0 and 1 (audio)
+or 2 (visual), so `audio_grad_sum` / `visual_grad_sum` are the existing statistics and the absent one reads 0.0.  The
+`fusion_module` the reference still constructs in these modes gets no gradient: it stays outside the arena, untouched.
+"""
+import ctypes
+
+import torch
+
+from . import _lib as L
+from .encoder import EncoderEngine
+from .trainer import ADAGRAD_INITIAL_ACCUMULATOR, DEFAULT_WEIGHT_DECAY, OPTIMIZERS, DGLTrainer, _chain_streams
+
+
+class UnimodalTrainer(DGLTrainer):
+    """A class of its own beside DGLTrainer (whose step it does not share); what it inherits is the part that does not know
+    the model: the optimizer state and its checkpoint (`state_dict` / `load_state_dict`), the statistics + clip + update tail
+    of the step, `grad(name)` and `close()`."""
+
+    def __init__(self, model, lr, momentum=0.9, weight_decay=None, max_norm=40.0, dtype=None, optimizer="sgd",
+                 process_group=None):
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"UnimodalTrainer: optimizer must be one of {OPTIMIZERS} (main.py --optimizer), got {optimizer!r}")
+        if process_group is not None:
+            raise L.GdlError("UnimodalTrainer: data-parallel runs (process_group) are not built for the unimodal baselines")
+        modality = getattr(model, "modality", None)
+        if modality == "full":
+            raise L.GdlError("UnimodalTrainer: modality='full' has both encoders -- use gdl.DGLTrainer (mode='dgl' or 'joint')")
+        if modality not in ("audio", "visual"):
+            raise L.GdlError(f"UnimodalTrainer: model.modality must be 'audio' or 'visual', got {modality!r}")
+        self.optimizer = optimizer
+        self.modality = modality
+        self.mode = "unimodal"
+        net = getattr(model, modality + "_net")
+        cls = getattr(model, modality + "_classifier")
+        self.device = cls.weight.device
+        if self.device.type != "cuda":
+            raise L.GdlError("UnimodalTrainer: the model must live on an MI355X (cuda) device; there is no CPU path")
+        if hasattr(net, "cfg") and hasattr(net, "num_features"):
+            raise L.GdlError("UnimodalTrainer: the Swin branch as the only modality is not built (ResNet18 encoders only)")
+        if tuple(cls.weight.shape[1:]) != (512,) or cls.weight.shape[0] > 512:
+            raise L.GdlError("UnimodalTrainer: the classifier must be Linear(512, n_classes <= 512)")
+        self.lib = L.load()
+        self.model, self.net = model, net
+        self.lr, self.mu, self.max_norm = float(lr), float(momentum), float(max_norm)
+        self.wd = float(DEFAULT_WEIGHT_DECAY[optimizer] if weight_decay is None else weight_decay)
+        self.dtype = dtype if dtype is not None else net.gdl_dtype
+        self.n_classes = cls.weight.shape[0]
+        self.reducer, self.world, self.pg = None, 1, None
+        named = [(modality + "_classifier.weight", cls.weight), (modality + "_classifier.bias", cls.bias)]
+        named += [(modality + "_net." + n, p) for n, p in net.named_parameters()]
+        if len(named) != 62:
+            raise L.GdlError("UnimodalTrainer: the encoder must be the ResNet18 mirror (60 tensors)")
+        self.nf = 2
+        self.names = [n for n, _ in named]
+        offs, o = [0], 0
+        for _, p in named:
+            o += p.numel()
+            offs.append(o)
+        self.offsets, self.total = offs, o
+        group = [0, 0] + [1 if modality == "audio" else 2] * 60
+        self.params = torch.empty(o, device=self.device)
+        self.grads = torch.zeros(o, device=self.device)
+        self.momentum = self.exp_avg = self.exp_avg_sq = self.state_sum = None
+        if optimizer == "sgd":
+            self.momentum = torch.zeros(o, device=self.device)
+        elif optimizer == "Adam":
+            self.exp_avg = torch.zeros(o, device=self.device)
+            self.exp_avg_sq = torch.zeros(o, device=self.device)
+        else:
+            self.state_sum = torch.full((o,), ADAGRAD_INITIAL_ACCUMULATOR, device=self.device)
+        self.pviews, self.gviews = [], []
+        for i, (_, p) in enumerate(named):
+            v = self.params[offs[i]:offs[i + 1]].view(p.shape)
+            v.copy_(p.data)
+            p.data = v  # the module now aliases the arena: state_dict / eval see the trained weights
+            self.pviews.append(v)
+            self.gviews.append(self.grads[offs[i]:offs[i + 1]].view(p.shape))
+        h = ctypes.c_void_p()
+        L.call("gdl_optim_create", ctypes.byref(h), (ctypes.c_int64 * len(offs))(*offs), (ctypes.c_int32 * len(group))(*group),
+               len(group))
+        self.opt = h
+        self.opt_ws_bytes = self.lib.gdl_optim_workspace_bytes(h)
+        self.opt_ws = torch.empty(max(self.opt_ws_bytes, 8), dtype=torch.uint8, device=self.device)
+        L.call("gdl_optim_bind_workspace", self.opt, L.ptr(self.opt_ws), self.opt_ws_bytes, L.cur_stream())
+        self.stats = torch.zeros(self.lib.gdl_optim_stats_len(h), device=self.device)
+        self.losses = torch.zeros(1, device=self.device)
+        # the process-wide chain streams (gdl.trainer._chain_streams: never a new one per trainer)
+        self.s_a, self.s_v = _chain_streams(self.device)
+        self.chain, self.lane = (self.s_a, self.s_v) if modality == "audio" else (self.s_v, self.s_a)
+        self.eng = None
+        self.steps = 0
+        self.phase_events = None
+        self.stats_log = self.stats_log_pos = None
+
+    def _replica_buffers(self):
+        return []
+
+    # ------------------------------------------------------------------ setup per batch shape
+    def _input(self, spec, image):
+        """The encoder's input of a (spec, image) pair; the other modality's tensor is ignored and may be None."""
+        x = spec if self.modality == "audio" else image
+        want = "spec [B,F,T']" if self.modality == "audio" else "image [B,3,T,H,W]"
+        if x is None or x.dim() != (3 if self.modality == "audio" else 5) or (self.modality == "visual" and x.shape[1] != 3):
+            raise L.GdlError(f"UnimodalTrainer: the {self.modality} model takes {want}")
+        if x.device != self.device:
+            raise L.GdlError(f"UnimodalTrainer: the input must be on {self.device}, got {x.device}")
+        return x.unsqueeze(1) if self.modality == "audio" else x  # main.py: spec.unsqueeze(1)
+
+    def _prepare(self, x):
+        key = tuple(x.shape)
+        if getattr(self, "_key", None) == key:
+            return
+        self._key = key
+        B = x.shape[0]
+        T, H, W = (1, x.shape[2], x.shape[3]) if self.modality == "audio" else tuple(x.shape[2:])
+        self.eng = EncoderEngine(self.modality, self.dtype, B, T, H, W, self.device)
+        n, d = self.n_classes, self.device
+        self.f, self.df = torch.empty((B, 512), device=d), torch.empty((B, 512), device=d)
+        self.out, self.dlogits = torch.empty((B, n), device=d), torch.empty((B, n), device=d)
+        self.B = B
+
+    def _bind(self):
+        bns = self.net._bn_layers()
+        self.eng.set_params([p.data for p in self.net.parameters()], [b.running_mean for b in bns],
+                            [b.running_var for b in bns], [b.num_batches_tracked for b in bns])
+
+    def _check_label(self, label):
+        if label.dtype != torch.int64 or label.dim() != 1 or label.shape[0] != self.B or label.device != self.device:
+            raise L.GdlError(f"UnimodalTrainer: label must be an int64 [B={self.B}] tensor on {self.device}, got "
+                             f"{label.dtype} {tuple(label.shape)} on {label.device}")
+
+    # ------------------------------------------------------------------ the step
+    def step(self, spec, image, label):
+        """DGLTrainer.step's argument order: spec [B,F,T'] float, image [B,3,T,H,W] float, label [B] int64, resident on the
+        device; the tensor of the modality the model does not have may be None."""
+        x = self._input(spec, image)
+        self._prepare(x)
+        self._check_label(label)
+        self._bind()
+        caller = torch.cuda.current_stream(self.device)
+        main, lane = self.chain, self.lane
+        self.eng.borrow_side_stream(lane.cuda_stream)
+        main.wait_stream(caller)
+        with torch.cuda.stream(main):
+            label = label.contiguous()
+            B, n, st = self.B, self.n_classes, main.cuda_stream
+            self._mark(main, "start")
+            self.eng.forward(x, True, feat_out=self.f)
+            self._mark(main, "fwd_done")
+            L.call("gdl_head_cls_ce", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.pviews[1]), L.ptr(label), 1.0,
+                   L.ptr(self.out), L.ptr(self.losses), L.ptr(self.dlogits), L.ptr(self.df), B, n, 512, st)
+            self._mark(main, "head_done")
+            ev = main.record_event()
+            # the classifier's own gradients need only dlogits and the features: on the lane, beside the encoder backward
+            lane.wait_event(ev)
+            with torch.cuda.stream(lane):
+                L.call("gdl_head_cls_bwd", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.dlogits), None, L.ptr(self.gviews[0]),
+                       L.ptr(self.gviews[1]), B, n, 512, lane.cuda_stream)
+                ev_cls = lane.record_event()
+            self.eng.backward(self.gviews[2:], dfeat=self.df)
+            main.wait_event(ev_cls)
+            self._finish_step(main, st)
+        caller.wait_stream(main)
+
+    # ------------------------------------------------------------------ validation (main.py's valid())
+    def valid(self, batches):
+        """Eval-mode forward (BatchNorm running statistics) of every (spec, image, label) batch, arg-max of `out` and the
+        per-class counters on the device, one host copy at the end.  The reference's valid() counts its three (identical) logit
+        sets: returns (acc, acc, acc); `valid_counts` rows = num, acc, acc, acc per class."""
+        n = self.n_classes
+        cnt = torch.zeros((2, n), dtype=torch.int64, device=self.device)
+        for spec, image, label in batches:
+            x = self._input(spec, image)
+            self._prepare(x)
+            self._check_label(label)
+            self._bind()
+            label = label.contiguous()
+            st = L.cur_stream()
+            self.eng.forward(x, False, feat_out=self.f)
+            L.call("gdl_head_cls_fwd", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.pviews[1]), L.ptr(self.out), self.B, n,
+                   512, st)
+            L.call("gdl_eval_count", L.ptr(self.out), None, None, L.ptr(label), self.B, n, cnt[0].data_ptr(), cnt[1].data_ptr(),
+                   None, None, st)
+        c = cnt.cpu().numpy().astype("float64")
+        self.valid_counts = c[[0, 1, 1, 1]]
+        acc = c[1].sum() / max(c[0].sum(), 1.0)
+        return acc, acc, acc
+
+    # ------------------------------------------------------------------ results (host sync)
+    def read(self):
+        """Synchronises and returns the quantities the reference prints / logs per step (its three losses are one)."""
+        torch.cuda.synchronize(self.device)
+        s = self.stats.cpu().numpy()
+        loss = float(self.losses.cpu().numpy()[0])
+        nseg = len(self.names)
+        r = {"loss_f": loss, "loss_a": loss, "loss_v": loss, "total_norm": float(s[0]), "clip_coef": float(s[1]),
+             "audio_grad_sum": float(s[2]), "visual_grad_sum": float(s[3]),
+             "grad_norm": dict(zip(self.names, s[4:4 + nseg].tolist())),
+             "grad_absmean": dict(zip(self.names, s[4 + nseg:4 + 2 * nseg].tolist())),
+             "out": self.out.cpu().numpy()}
+        # (a diverged BatchNorm must be as loud as the reference's inf / NaN: DGLTrainer.read)
+        bad = self.eng.bn_overflow() if self.eng is not None else 0
+        if bad:
+            raise FloatingPointError(f"gdl: the statistics of {bad} BatchNorm layer(s) overflowed in the last training forward "
+                                     "(activations of mean magnitude beyond 8192: the run has diverged)")
+        return r

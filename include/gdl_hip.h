@@ -283,7 +283,25 @@ GDL_API int gdl_head_uni_dfeat(const float* f, const float* Wp, int ldw, const f
  * Wp = W + 512 with ldw = 512 + 768); df bit-identical to gdl_head_concat_xy_fwd + gdl_softmax_ce3 + gdl_head_concat_xy_bwd. */
 GDL_API int gdl_head_uni_dfeat_w(const float* f, const float* Wp, int ldw, const float* bp, const int64_t* labels, float scale,
                                  float* df, int B, int n_classes, int width, void* stream);
-/* The same head with unequal feature widths, W [n][x_dim + y_dim] (512 audio + 768 Swin features; the reference's
+/* The classifier of the unimodal baselines (AVClassifier_DGL with modality 'audio' / 'visual', basic_model.py:46-59, 88-122:
+ * nn.Linear(512, n_classes) on the pooled features of the one encoder, trained by main.py's single CrossEntropyLoss).
+ * float32: f [B][width], W [n][width], b [n]; width must be 512 and n_classes <= 512 (other sizes: GDL_ERR_ARG).
+ *   gdl_head_cls_fwd: out = f W^T + b.
+ *   gdl_head_cls_bwd: for an upstream gradient g_out [B][n]: df = g_out W, dW = g_out^T f, db = sum_b g_out; each of the three
+ *     outputs may be NULL and is then neither computed nor touched.
+ *   gdl_head_cls_ce: ONE launch for the training step -- out, loss[0] = mean CE(out, labels), dlogits = scale * (softmax(out) -
+ *     onehot) / B and df = dlogits W.  out, dlogits and df are bit-identical to gdl_head_cls_fwd + gdl_softmax_ce +
+ *     gdl_head_cls_bwd; loss[0] sums the B per-sample terms in one fixed order (no floating-point atomics): every output is
+ *     bit-reproducible from run to run.  A label outside [0, n) gives no one-hot term and a NaN loss, as in gdl_softmax_ce.
+ *     The launch keeps B floats and a counter of its own per (device, stream); the first call on a stream (and the first with a
+ *     larger B) allocates them and synchronises the device, every later call is asynchronous. */
+GDL_API int gdl_head_cls_fwd(const float* f, const float* W, const float* b, float* out, int B, int n_classes, int width,
+                             void* stream);
+GDL_API int gdl_head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B,
+                             int n_classes, int width, void* stream);
+GDL_API int gdl_head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out,
+                            float* loss, float* dlogits, float* df, int B, int n_classes, int width, void* stream);
+/* The concat head with unequal feature widths, W [n][x_dim + y_dim] (512 audio + 768 Swin features; the reference's
  * ConcatFusion_Swin, fusion_modules.py:79-88, in its DGL form :45-59): same contract as the two calls above. */
 GDL_API int gdl_head_concat_xy_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out,
                                    float* y_out, int B, int n_classes, int x_dim, int y_dim, void* stream);
