@@ -9,6 +9,7 @@
 // W[:, 512:].y, so one launch produces all of them.  Sizes are tiny (B x 1024 x n_classes):
 // latency bound, no MFMA.
 #include "common.h"
+#include "head_body.h"
 #include "prof.h"
 
 namespace gdl {
@@ -421,83 +422,18 @@ __device__ __forceinline__ void softmax_ce_block(const float* __restrict__ logit
 // head_bwd_feat_kernel use: df is bit-identical to the three-launch path.
 // Round 5: 16 waves per sample and no serial walk beyond the sums whose order is the contract (at 309 classes x 768 features
 // the four-wave form -- 78 classes per wave one after the other, thread 0 alone through max / exp / sum, 927 dependent
-// loads per thread for df -- took 113-131 us ON the chain between an encoder's forward and its backward): the classes go
-// round the 16 waves two at a time, max and exp are evaluated by all threads (max is exact in any order; the exponentials
-// are the same values) and only their SUM is walked in class order by one thread, df keeps its ascending walk per feature
-// with eight weight loads in flight.  113 -> 28 us there (kernel trace, in the step).
+// loads per thread for df -- took 113-131 us ON the chain between an encoder's forward and its backward): the schedule of
+// head_ce_body (head_body.h), which this kernel is.  113 -> 28 us there (kernel trace, in the step).
 template <int ND>  // feature width = 64 ND
 __global__ __launch_bounds__(1024) void head_uni_dfeat_kernel(const float* __restrict__ f, const float* __restrict__ Wp, int ldw,
                                                              const float* __restrict__ bp, const int64_t* __restrict__ labels,
                                                              float scale, float* __restrict__ df, int B, int n) {
-    constexpr int D = 64 * ND, NW = 16;
-    __shared__ float lg[512], dl[512], ex[512];
-    __shared__ float wmx[NW];
-    __shared__ float lse_s;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float fv[ND];
-#pragma unroll
-    for (int i = 0; i < ND; ++i) fv[i] = f[(size_t)b * D + lane + 64 * i];
-    for (int j = wave; j < n; j += 2 * NW) {
-        const int j2 = j + NW;
-        const float* w = Wp + (size_t)j * ldw;
-        const float* w2 = Wp + (size_t)(j2 < n ? j2 : j) * ldw;
-        float pa = 0.f, pb = 0.f;
-#pragma unroll
-        for (int i = 0; i < ND; ++i) pa += w[lane + 64 * i] * fv[i];
-#pragma unroll
-        for (int i = 0; i < ND; ++i) pb += w2[lane + 64 * i] * fv[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            pa += __shfl_xor(pa, o);
-            pb += __shfl_xor(pb, o);
-        }
-        if (lane == 0) {
-            lg[j] = pa + bp[j];
-            if (j2 < n) lg[j2] = pb + bp[j2];
-        }
-    }
-    __syncthreads();
-    {
-        float mx = -INFINITY;
-        for (int j = threadIdx.x; j < n; j += 1024) mx = fmaxf(mx, lg[j]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        if (lane == 0) wmx[wave] = mx;
-    }
-    __syncthreads();
-    float mx = wmx[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, wmx[w]);
-    for (int j = threadIdx.x; j < n; j += 1024) ex[j] = expf(lg[j] - mx);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float se = 0.f;
-        for (int j = 0; j < n; ++j) se += ex[j];
-        lse_s = mx + logf(se);
-    }
-    __syncthreads();
-    const long lab64 = (long)labels[b];
-    const int lab = (lab64 >= 0 && lab64 < n) ? (int)lab64 : -1;
-    for (int j = threadIdx.x; j < n; j += 1024) dl[j] = scale * (expf(lg[j] - lse_s) - (j == lab ? 1.f : 0.f)) / (float)B;
-    __syncthreads();
-    for (int i = threadIdx.x; i < D; i += 1024) {
-        const float* w = Wp + i;
-        float s2 = 0.f;
-        int j = 0;
-        for (; j + 8 <= n; j += 8) {
-            float q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = w[(size_t)(j + u) * ldw];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s2 += dl[j + u] * q[u];
-        }
-        for (; j < n; ++j) s2 += dl[j] * w[(size_t)j * ldw];
-        df[(size_t)b * D + i] = s2;
-    }
+    __shared__ HeadBodyLds s;
+    head_ce_body<ND, false>(s, f, Wp, ldw, bp, labels, scale, nullptr, nullptr, df, B, n);
 }
 int head_uni_dfeat(const float* f, const float* Wp, int ldw, const float* bp, const int64_t* labels, float scale, float* df, int B,
                    int n, int width, hipStream_t st) {
-    GDL_REQUIRE(n <= 512, "head_uni_dfeat: at most 512 classes");
+    GDL_REQUIRE(n <= HB_MAXN, "head_uni_dfeat: at most %d classes", HB_MAXN);
     GDL_REQUIRE(width == 512 || width == 768 || width == 1024, "head_uni_dfeat: feature width %d (512, 768 or 1024)", width);
     ProfScope prof("gdl::head_uni_dfeat_kernel", PROF_HBM, st, (double)B * width * 8.0 + (double)n * width * 4.0);
     if (width == 512)

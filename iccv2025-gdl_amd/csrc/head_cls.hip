@@ -9,18 +9,15 @@
 // forward and its backward in the training step (logits, loss, dlogits and df), where head_uni_dfeat_kernel stands in the
 // DGL step.  Sizes are tiny (B x 512 x n): latency bound, no MFMA.
 //
-// Every sum has ONE order, shared by the three launchers through the device functions below, so head_cls_ce's out, dlogits
-// and df carry the bits of head_cls_fwd + softmax_ce (head.hip) + head_cls_bwd:
-//   a logit      : lane l of a wave adds f[l + 64 i] * W[j][l + 64 i] for i = 0 .. 7 (fmaf chain), xor butterfly 32 .. 1, + b[j]
-//   softmax / CE : softmax_ce_block's -- max (exact in any order), expf(l - max) summed in class order, lse = max + logf(sum),
-//                  dlogits = scale * (expf(l - lse) - onehot) / B
-//   df[i]        : classes in ascending order (fmaf chain), eight weight loads in flight
-//   dW / db      : samples in ascending order
+// Every sum has ONE order, shared by the three launchers through the device functions of head_body.h, so head_cls_ce's out,
+// dlogits and df carry the bits of head_cls_fwd + softmax_ce (head.hip) + head_cls_bwd (the orders: head_body.h; dW / db:
+// samples in ascending order).
 #include <map>
 #include <mutex>
 #include <utility>
 
 #include "common.h"
+#include "head_body.h"
 #include "ops.h"
 #include "prof.h"
 
@@ -28,41 +25,7 @@ namespace gdl {
 
 constexpr int CLS_D = 512;   // feature width
 constexpr int CLS_ND = 8;    // features per lane
-constexpr int CLS_MAXN = 512;
-
-__device__ __forceinline__ void cls_load_feat(const float* __restrict__ f, int lane, float (&fv)[CLS_ND]) {
-#pragma unroll
-    for (int i = 0; i < CLS_ND; ++i) fv[i] = f[lane + 64 * i];
-}
-// the lane's share of two logits at a time (their loads and butterflies overlap); every lane returns the full sums
-__device__ __forceinline__ void cls_dot2(const float* __restrict__ w, const float* __restrict__ w2, const float (&fv)[CLS_ND], int lane,
-                                         float& pa, float& pb) {
-    pa = 0.f, pb = 0.f;
-#pragma unroll
-    for (int i = 0; i < CLS_ND; ++i) pa = fmaf(w[lane + 64 * i], fv[i], pa);
-#pragma unroll
-    for (int i = 0; i < CLS_ND; ++i) pb = fmaf(w2[lane + 64 * i], fv[i], pb);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        pa += __shfl_xor(pa, o);
-        pb += __shfl_xor(pb, o);
-    }
-}
-// df[i] = sum_j g[j] W[j][i], classes ascending; g in LDS
-__device__ __forceinline__ float cls_df_walk(const float* g, const float* __restrict__ W, int i, int n) {
-    const float* w = W + i;
-    float s = 0.f;
-    int j = 0;
-    for (; j + 8 <= n; j += 8) {
-        float q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = w[(size_t)(j + u) * CLS_D];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s = fmaf(g[j + u], q[u], s);
-    }
-    for (; j < n; ++j) s = fmaf(g[j], w[(size_t)j * CLS_D], s);
-    return s;
-}
+constexpr int CLS_MAXN = HB_MAXN;
 
 // ---------------------------------------------------------------- forward
 // grid = (B, ceil(n / 8)): a block's four waves own eight classes of one sample, two per wave
@@ -73,9 +36,9 @@ __global__ __launch_bounds__(256) void head_cls_fwd_kernel(const float* __restri
     const int j = blockIdx.y * CLS_FWD_CH + wave, j2 = j + 4;
     if (j >= n) return;
     float fv[CLS_ND];
-    cls_load_feat(f + (size_t)b * CLS_D, lane, fv);
+    head_load_feat<CLS_ND>(f + (size_t)b * CLS_D, lane, fv);
     float pa, pb;
-    cls_dot2(W + (size_t)j * CLS_D, W + (size_t)(j2 < n ? j2 : j) * CLS_D, fv, lane, pa, pb);
+    head_dot2<CLS_ND>(W + (size_t)j * CLS_D, W + (size_t)(j2 < n ? j2 : j) * CLS_D, fv, lane, pa, pb);
     if (lane == 0) {
         out[(size_t)b * n + j] = pa + bias[j];
         if (j2 < n) out[(size_t)b * n + j2] = pb + bias[j2];
@@ -97,7 +60,7 @@ __global__ __launch_bounds__(256) void head_cls_dfeat_kernel(const float* __rest
     for (int j = threadIdx.x; j < n; j += 256) g[j] = g_out[(size_t)b * n + j];
     __syncthreads();
     const int i = blockIdx.y * 256 + threadIdx.x;
-    df[(size_t)b * CLS_D + i] = cls_df_walk(g, W, i, n);
+    df[(size_t)b * CLS_D + i] = head_df_walk(g, W, CLS_D, i, n);
 }
 // grid = (n, 2): a thread per weight-gradient element; the batch's gradients of class j staged in LDS 256 samples at a time,
 // summed in sample order; db[j] = their plain sum in the same order (the y = 0 block)
@@ -137,9 +100,8 @@ int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, 
 }
 
 // ---------------------------------------------------------------- the training step's launch
-// grid = B, 16 waves per sample: head_uni_dfeat_kernel's schedule (head.hip: the classes go round the 16 waves two at a time,
-// max and exp by all threads, only the sum of the exponentials walked in class order by one thread, df an ascending walk per
-// feature by the first 512 threads) plus the three stores the unimodal step needs -- out, dlogits and the sample's loss term.
+// grid = B, 16 waves per sample: head_ce_body (head_body.h; head_uni_dfeat_kernel<8> in the DGL step is the same body) plus the
+// three stores the unimodal step needs -- out and dlogits (the body's STORE) and the sample's loss term.
 //
 // The mean over the samples = over the blocks.  df occupies waves 0 .. 7 only; wave 15, idle by then, publishes the sample's
 // term (lse - logit[label]) and draws a ticket; the block whose ticket is the last sums all B terms in ONE order (lane l takes
@@ -154,73 +116,24 @@ __global__ __launch_bounds__(1024) void head_cls_ce_kernel(const float* __restri
                                                           float scale, float* __restrict__ out, float* __restrict__ loss,
                                                           float* __restrict__ dlogits, float* __restrict__ df,
                                                           float* __restrict__ part, unsigned* __restrict__ cnt, int B, int n) {
-    constexpr int NW = 16;
-    __shared__ float lg[CLS_MAXN], dl[CLS_MAXN], ex[CLS_MAXN];
-    __shared__ float wmx[NW];
-    __shared__ float lse_s;
+    __shared__ HeadBodyLds s;
+    const int lab = head_ce_body<CLS_ND, true>(s, f, W, CLS_D, bias, labels, scale, out, dlogits, df, B, n);
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float fv[CLS_ND];
-    cls_load_feat(f + (size_t)b * CLS_D, lane, fv);
-    for (int j = wave; j < n; j += 2 * NW) {
-        const int j2 = j + NW;
-        float pa, pb;
-        cls_dot2(W + (size_t)j * CLS_D, W + (size_t)(j2 < n ? j2 : j) * CLS_D, fv, lane, pa, pb);
-        if (lane == 0) {
-            lg[j] = pa + bias[j];
-            if (j2 < n) lg[j2] = pb + bias[j2];
-        }
-    }
-    __syncthreads();
-    {
-        float mx = -INFINITY;
-        for (int j = threadIdx.x; j < n; j += 1024) {
-            const float l = lg[j];
-            out[(size_t)b * n + j] = l;
-            mx = fmaxf(mx, l);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        if (lane == 0) wmx[wave] = mx;
-    }
-    __syncthreads();
-    float mx = wmx[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, wmx[w]);
-    for (int j = threadIdx.x; j < n; j += 1024) ex[j] = expf(lg[j] - mx);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float se = 0.f;
-        for (int j = 0; j < n; ++j) se += ex[j];
-        lse_s = mx + logf(se);
-    }
-    __syncthreads();
-    // a class index outside [0, n) (a device assert in the reference's CrossEntropyLoss): no one-hot term, NaN in the loss
-    const long lab64 = (long)labels[b];
-    const int lab = (lab64 >= 0 && lab64 < n) ? (int)lab64 : -1;
-    const float lse = lse_s;
-    for (int j = threadIdx.x; j < n; j += 1024) {
-        const float d = scale * (expf(lg[j] - lse) - (j == lab ? 1.f : 0.f)) / (float)B;
-        dl[j] = d;
-        dlogits[(size_t)b * n + j] = d;
-    }
-    __syncthreads();  // (the last barrier: from here on the waves part ways)
-    if (threadIdx.x < CLS_D) {
-        df[(size_t)b * CLS_D + threadIdx.x] = cls_df_walk(dl, W, threadIdx.x, n);
-    } else if (wave == NW - 1) {
+    if (wave == HB_NW - 1) {  // (beyond the df walk's threads)
         int last = 0;
         if (lane == 0) {
-            st_agent(part + b, lab >= 0 ? lse - lg[lab] : __builtin_nanf(""));
+            st_agent(part + b, lab >= 0 ? s.lse - s.lg[lab] : __builtin_nanf(""));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(B - 1);
         }
         last = __shfl(last, 0);
         if (last) {
-            float s = 0.f;
-            for (int k = lane; k < B; k += 64) s += __hip_atomic_load(part + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            float t = 0.f;
+            for (int k = lane; k < B; k += 64) t += __hip_atomic_load(part + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
             if (lane == 0) {
-                loss[0] = s / (float)B;
+                loss[0] = t / (float)B;
                 __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }

@@ -22,6 +22,10 @@ every data-parallel run):
       [+ per-bucket RCCL all-reduce as soon as a bucket is final]
   grad statistics, clip + SGD as above
 
+ArenaTrainer below is what such a runner is before it knows its model (the flat arenas, the optimizer state and its checkpoint,
+the chain streams, the statistics + clip + update tail); DGLTrainer is the step above on it, gdl.unimodal.UnimodalTrainer the
+one-encoder step.
+
 The result is numerically the reference's two-phase backward: SURVEY section 0 shows the
 single-pass form is bit-identical in exact arithmetic, and tests/test_step_gpu.py checks it
 against golden vectors of the reference.
@@ -88,23 +92,192 @@ def _chain_streams(device):
     return _CHAIN_STREAMS[key]
 
 
-class DGLTrainer:
+class ArenaTrainer:
+    """What a native step runner is before it knows its model: the trained tensors laid out in one flat parameter arena and one
+    gradient arena (the modules alias the former), the chosen optimizer's state arenas and their checkpoint, the library's
+    optimizer descriptor, the two chain streams, and the tail of every step -- gradient statistics, clip, update.  A subclass
+    supplies the (name, parameter) list with its optimizer groups (0 = head, 1 = audio encoder, 2 = visual encoder: the
+    statistics' `audio_grad_sum` / `visual_grad_sum`) and the body of the step in front of `_finish_step`."""
+
+    _script = "main_dgl.py"  # the reference script whose --optimizer the class takes
+
+    @classmethod
+    def _check_optimizer(cls, optimizer):
+        """(subclasses call this before they touch the model: a wrong name is refused first)"""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"{cls.__name__}: optimizer must be one of {OPTIMIZERS} ({cls._script} --optimizer), got {optimizer!r}")
+
+    def __init__(self, named, group, device, optimizer, lr, momentum, weight_decay, max_norm):
+        """named: [(name, parameter)] in arena order; group: the optimizer group of each; optimizer: the scripts'
+        `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay None = the reference's value
+        for that optimizer (DEFAULT_WEIGHT_DECAY); `momentum` applies to "sgd" only."""
+        self._check_optimizer(optimizer)
+        self.optimizer = optimizer
+        if weight_decay is None:
+            weight_decay = DEFAULT_WEIGHT_DECAY[optimizer]
+        self.lib = L.load()
+        self.device = device
+        self.lr, self.mu, self.wd, self.max_norm = float(lr), float(momentum), float(weight_decay), float(max_norm)
+        self.names = [n for n, _ in named]
+        offs, o = [0], 0
+        for _, p in named:
+            o += p.numel()
+            offs.append(o)
+        self.offsets = offs
+        self.total = o
+        self.params = torch.empty(o, device=self.device)
+        self.grads = torch.zeros(o, device=self.device)
+        # optimizer state arenas (the parameter arena's layout), only those of the chosen optimizer
+        self.momentum = self.exp_avg = self.exp_avg_sq = self.state_sum = None
+        if optimizer == "sgd":
+            self.momentum = torch.zeros(o, device=self.device)
+        elif optimizer == "Adam":
+            self.exp_avg = torch.zeros(o, device=self.device)
+            self.exp_avg_sq = torch.zeros(o, device=self.device)
+        else:
+            self.state_sum = torch.full((o,), ADAGRAD_INITIAL_ACCUMULATOR, device=self.device)
+        self.pviews, self.gviews = [], []
+        for i, (_, p) in enumerate(named):
+            v = self.params[offs[i]:offs[i + 1]].view(p.shape)
+            v.copy_(p.data)
+            p.data = v  # the module now aliases the arena: state_dict / eval see the trained weights
+            self.pviews.append(v)
+            self.gviews.append(self.grads[offs[i]:offs[i + 1]].view(p.shape))
+        h = ctypes.c_void_p()
+        so = (ctypes.c_int64 * len(offs))(*offs)
+        sg = (ctypes.c_int32 * len(group))(*group)
+        L.call("gdl_optim_create", ctypes.byref(h), so, sg, len(group))
+        self.opt = h
+        self.opt_ws_bytes = self.lib.gdl_optim_workspace_bytes(h)
+        self.opt_ws = torch.empty(max(self.opt_ws_bytes, 8), dtype=torch.uint8, device=self.device)
+        # (explicit: a caching allocator may hand out a block at the address of an earlier trainer's workspace)
+        L.call("gdl_optim_bind_workspace", self.opt, L.ptr(self.opt_ws), self.opt_ws_bytes, L.cur_stream())
+        self.stats = torch.zeros(self.lib.gdl_optim_stats_len(h), device=self.device)
+        # The two chain streams are shared by every trainer of a process on this device: torch hands out a NEW pool stream per
+        # torch.cuda.Stream() call and never retires one, and once more distinct streams have carried work than the runtime has
+        # hardware queues (four), two chains can end up time-slicing one queue -- the third trainer built in a process ran its step
+        # 15 % slower than the same trainer in a fresh process (bench.py's `extra_workloads.ks`: 7.33 vs 6.36 ms, round 4).
+        self.s_a, self.s_v = _chain_streams(self.device)
+        # a data-parallel subclass sets both: `_finish_step` waits for the reducer and scales by 1 / world, `close` releases it
+        self.reducer = None
+        self.world = 1
+        self.steps = 0
+        self.phase_events = None  # set to [] to record (name, event) marks on the main stream per step
+        # measuring tap (bench.py): a [n, 2] device tensor + a position; while the position is not None every step copies its
+        # (total norm, clip coefficient) into the next row, device to device on the step's stream
+        self.stats_log = None
+        self.stats_log_pos = None
+
+    def _opt_state(self):
+        """{name: arena} of the chosen optimizer's state: momentum (sgd), exp_avg + exp_avg_sq (Adam), state_sum (AdaGrad)."""
+        names = {"sgd": ("momentum",), "Adam": ("exp_avg", "exp_avg_sq"), "AdaGrad": ("state_sum",)}[self.optimizer]
+        return {n: getattr(self, n) for n in names}
+
+    def state_dict(self):
+        """Optimizer-side state a reference checkpoint keeps besides model.state_dict() (optimizer.state_dict() /
+        scheduler, main_dgl.py:372): the optimizer's kind and state arenas, learning rate, step count (which the Adam bias
+        corrections count from)."""
+        return {"optimizer": self.optimizer, **{k: v.detach().clone() for k, v in self._opt_state().items()}, "lr": self.lr,
+                "steps": self.steps, "names": list(self.names), "offsets": list(self.offsets), "mu": self.mu,
+                "weight_decay": self.wd}
+
+    def load_state_dict(self, sd):
+        who = type(self).__name__
+        if list(sd["offsets"]) != list(self.offsets) or list(sd["names"]) != list(self.names):
+            raise L.GdlError(f"{who}.load_state_dict: the checkpoint's parameter layout differs from this model's")
+        kind = sd.get("optimizer", "sgd")  # (checkpoints written before the optimizer switch are SGD's)
+        if kind != self.optimizer:
+            raise L.GdlError(f"{who}.load_state_dict: the checkpoint holds {kind!r} state, this trainer runs {self.optimizer!r}")
+        for k, v in self._opt_state().items():
+            v.copy_(sd[k].to(self.device))
+        self.lr, self.steps = float(sd["lr"]), int(sd["steps"])
+
+    def close(self):
+        """Releases what the trainer owns outside PyTorch's allocator: the optimizer descriptor and, for
+        comm_backend="abi", the RCCL communicator (ncclCommDestroy).  Idempotent; also run by __del__."""
+        if getattr(self, "reducer", None) is not None:
+            self.reducer.close()
+        if getattr(self, "opt", None):
+            self.lib.gdl_optim_destroy(self.opt)
+            self.opt = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_label(self, label):
+        """The loss kernels index logits by label: require the reference's dtype and shape (a class index outside
+        [0, n) raises a device assert in the reference; here the loss kernel skips the sample and poisons the loss)."""
+        if label.dtype != torch.int64 or label.dim() != 1 or label.shape[0] != self.B or label.device != self.device:
+            raise L.GdlError(f"{type(self).__name__}: label must be an int64 [B={self.B}] tensor on {self.device}, got "
+                             f"{label.dtype} {tuple(label.shape)} on {label.device}")
+
+    def _finish_step(self, main, st):
+        """Joins the chains (and the collectives), then gradient statistics + clip + the optimizer's update on `main`."""
+        red = self.reducer
+        main.wait_stream(self.s_a)
+        main.wait_stream(self.s_v)
+        if red is not None:
+            red.wait_all()
+        self._mark(main, "bwd_done")
+        gs = 1.0 / self.world
+        L.call("gdl_optim_grad_stats", self.opt, L.ptr(self.grads), self.max_norm, gs, L.ptr(self.stats),
+               L.ptr(self.opt_ws), self.opt_ws_bytes, st)
+        if self.optimizer == "sgd":
+            L.call("gdl_optim_sgd_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.momentum),
+                   L.ptr(self.stats), gs, self.lr, self.mu, self.wd, st)
+        elif self.optimizer == "Adam":
+            L.call("gdl_optim_adamw_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.exp_avg),
+                   L.ptr(self.exp_avg_sq), L.ptr(self.stats), gs, self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, self.wd,
+                   self.steps + 1, st)
+        else:
+            L.call("gdl_optim_adagrad_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.state_sum),
+                   L.ptr(self.stats), gs, self.lr, ADAGRAD_EPS, self.wd, self.steps + 1, st)
+        self._mark(main, "end")
+        if self.stats_log is not None and self.stats_log_pos is not None and self.stats_log_pos < self.stats_log.shape[0]:
+            self.stats_log[self.stats_log_pos].copy_(self.stats[:2], non_blocking=True)
+            self.stats_log_pos += 1
+        self.steps += 1
+
+    def _mark(self, stream, name):
+        if self.phase_events is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(stream)
+            self.phase_events.append((name, e))
+
+    def _read_stats(self, engines):
+        """The part of read() every runner shares: synchronises, returns the step's gradient statistics, and raises if a
+        BatchNorm layer of one of `engines` overflowed."""
+        torch.cuda.synchronize(self.device)
+        s = self.stats.cpu().numpy()
+        nseg = len(self.names)
+        # a diverged BatchNorm (statistics beyond the fixed-point headroom, csrc/bnacc.h) must be as loud as the reference's
+        # inf / NaN: ReLU turns the NaN statistics' outputs into zeros, so the logits alone may look sane
+        bad = sum(e.bn_overflow() for e in engines if e is not None and hasattr(e, "bn_overflow"))
+        if bad:
+            raise FloatingPointError(f"gdl: the statistics of {bad} BatchNorm layer(s) overflowed in the last training forward "
+                                     "(activations of mean magnitude beyond 8192: the run has diverged)")
+        return {"total_norm": float(s[0]), "clip_coef": float(s[1]), "audio_grad_sum": float(s[2]),
+                "visual_grad_sum": float(s[3]), "grad_norm": dict(zip(self.names, s[4:4 + nseg].tolist())),
+                "grad_absmean": dict(zip(self.names, s[4 + nseg:4 + 2 * nseg].tolist()))}
+
+    def grad(self, name):
+        return self.gviews[self.names.index(name)]
+
+
+class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd"):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
         None = the reference's value for that optimizer (DEFAULT_WEIGHT_DECAY); `momentum` applies to "sgd" only."""
-        if optimizer not in OPTIMIZERS:
-            raise ValueError(f"DGLTrainer: optimizer must be one of {OPTIMIZERS} (main_dgl.py --optimizer), got {optimizer!r}")
-        self.optimizer = optimizer
-        if weight_decay is None:
-            weight_decay = DEFAULT_WEIGHT_DECAY[optimizer]
-        self.lib = L.load()
+        self._check_optimizer(optimizer)
         self.model = model
         self.mode = mode
-        self.lr, self.alpha, self.mu, self.wd, self.max_norm = float(lr), float(alpha), float(momentum), \
-            float(weight_decay), float(max_norm)
+        self.alpha = float(alpha)
         self.pg = process_group
         # visual_side_stream: None = the visual encoder's weight gradients get a stream of their own unless a process group is
         # given (the collective's stream is then the fourth); True / False force it.  Measured with a ONE-rank RCCL group on one
@@ -136,8 +309,8 @@ class DGLTrainer:
         self.head = ("gated" if hasattr(head, "fc_out") else "sum") if hasattr(head, "fc_x") else \
             ("film" if hasattr(head, "fc") else "concat")
         first = head.fc_x if self.head == "sum" else head.fc_out
-        self.device = first.weight.device
-        if self.device.type != "cuda":
+        device = first.weight.device
+        if device.type != "cuda":
             raise L.GdlError("DGLTrainer: the model must live on an MI355X (cuda) device; there is no CPU path")
         # mode: "dgl" = the step of main_dgl.py; "joint" (or its older name "concat") = the single-loss step of the jointly
         # trained model (main.py:161-175): every head tensor and both encoders learn from CE(out) alone
@@ -170,32 +343,9 @@ class DGLTrainer:
             raise L.GdlError("DGLTrainer: the Swin visual branch is built for the concat DGL head")
         if not self.vis_swin and self.nv != 60:
             raise L.GdlError("DGLTrainer: visual_net must be the ResNet18 mirror or the SwinTransformer mirror")
-        self.names = [n for n, _ in named]
-        offs, o = [0], 0
-        for _, p in named:
-            o += p.numel()
-            offs.append(o)
-        self.offsets = offs
-        self.total = o
         group = [0] * nf + [1] * 60 + [2] * self.nv
-        self.params = torch.empty(o, device=self.device)
-        self.grads = torch.zeros(o, device=self.device)
-        # optimizer state arenas (the parameter arena's layout), only those of the chosen optimizer
-        self.momentum = self.exp_avg = self.exp_avg_sq = self.state_sum = None
-        if optimizer == "sgd":
-            self.momentum = torch.zeros(o, device=self.device)
-        elif optimizer == "Adam":
-            self.exp_avg = torch.zeros(o, device=self.device)
-            self.exp_avg_sq = torch.zeros(o, device=self.device)
-        else:
-            self.state_sum = torch.full((o,), ADAGRAD_INITIAL_ACCUMULATOR, device=self.device)
-        self.pviews, self.gviews = [], []
-        for i, (_, p) in enumerate(named):
-            v = self.params[offs[i]:offs[i + 1]].view(p.shape)
-            v.copy_(p.data)
-            p.data = v  # the module now aliases the arena: state_dict / eval see the trained weights
-            self.pviews.append(v)
-            self.gviews.append(self.grads[offs[i]:offs[i + 1]].view(p.shape))
+        super().__init__(named, group, device, optimizer, lr, momentum, weight_decay, max_norm)
+        offs = self.offsets
         # all-reduce buckets (ranges of the flat gradient arena).  layer4 = the last 15 tensors of an encoder, 8.4 M
         # of its 11.2 M parameters, is final right after the first two blocks of the backward: its own bucket lets
         # three quarters of the exchange overlap the rest of the backward.
@@ -207,8 +357,6 @@ class DGLTrainer:
         self.bucket = {"fusion": (0, offs[nf]),
                        "audio_l4": (offs[a0 + 45], offs[a0 + 60]), "audio_rest": (offs[a0], offs[a0 + 45]),
                        "visual_l4": (offs[vsplit], offs[v0 + self.nv]), "visual_rest": (offs[v0], offs[vsplit])}
-        self.reducer = None
-        self.world = 1
         if process_group is not None:
             from .ddp import BucketReducer
 
@@ -218,29 +366,8 @@ class DGLTrainer:
             # that differs between ranks or a rank-0-only checkpoint load must not diverge silently.  fc_auxi (and the
             # gated head's fc_x / fc_y) live outside the arena: they are never updated but still part of the state.
             self.reducer.sync_state([self.params] + list(self._opt_state().values()) + self._replica_buffers())
-        h = ctypes.c_void_p()
-        so = (ctypes.c_int64 * len(offs))(*offs)
-        sg = (ctypes.c_int32 * len(group))(*group)
-        L.call("gdl_optim_create", ctypes.byref(h), so, sg, len(group))
-        self.opt = h
-        self.opt_ws_bytes = self.lib.gdl_optim_workspace_bytes(h)
-        self.opt_ws = torch.empty(max(self.opt_ws_bytes, 8), dtype=torch.uint8, device=self.device)
-        # (explicit: a caching allocator may hand out a block at the address of an earlier trainer's workspace)
-        L.call("gdl_optim_bind_workspace", self.opt, L.ptr(self.opt_ws), self.opt_ws_bytes, L.cur_stream())
-        self.stats = torch.zeros(self.lib.gdl_optim_stats_len(h), device=self.device)
         self.losses = torch.zeros(3, device=self.device)  # loss_f, loss_a, loss_v
-        # The two chain streams are shared by every trainer of a process on this device: torch hands out a NEW pool stream per
-        # torch.cuda.Stream() call and never retires one, and once more distinct streams have carried work than the runtime has
-        # hardware queues (four), two chains can end up time-slicing one queue -- the third trainer built in a process ran its step
-        # 15 % slower than the same trainer in a fresh process (bench.py's `extra_workloads.ks`: 7.33 vs 6.36 ms, round 4).
-        self.s_a, self.s_v = _chain_streams(self.device)
         self.eng_a = self.eng_v = None
-        self.steps = 0
-        self.phase_events = None  # set to [] to record (name, event) marks on the main stream per step
-        # measuring tap (bench.py): a [n, 2] device tensor + a position; while the position is not None every step copies its
-        # (total norm, clip coefficient) into the next row, device to device on the step's stream
-        self.stats_log = None
-        self.stats_log_pos = None
 
     def _replica_buffers(self):
         """Every tensor of the replica that is not in the flat arenas: BatchNorm running statistics and counters of
@@ -256,52 +383,19 @@ class DGLTrainer:
         if self.reducer is not None:
             self.reducer.broadcast_buffers(self._replica_buffers())
 
-    def _opt_state(self):
-        """{name: arena} of the chosen optimizer's state: momentum (sgd), exp_avg + exp_avg_sq (Adam), state_sum (AdaGrad)."""
-        names = {"sgd": ("momentum",), "Adam": ("exp_avg", "exp_avg_sq"), "AdaGrad": ("state_sum",)}[self.optimizer]
-        return {n: getattr(self, n) for n in names}
-
     def state_dict(self):
-        """Optimizer-side state a reference checkpoint keeps besides model.state_dict() (optimizer.state_dict() /
-        scheduler, main_dgl.py:372): the optimizer's kind and state arenas, learning rate, step count (which the Adam bias
-        corrections count from).  In data-parallel mode the BatchNorm buffers are first made rank 0's, so model.state_dict()
-        taken next is the reference's replica-0 state."""
+        """In data-parallel mode the BatchNorm buffers are first made rank 0's, so model.state_dict() taken next is the
+        reference's replica-0 state."""
         self.sync_replicas()
-        return {"optimizer": self.optimizer, **{k: v.detach().clone() for k, v in self._opt_state().items()}, "lr": self.lr,
-                "steps": self.steps, "names": list(self.names), "offsets": list(self.offsets), "mu": self.mu,
-                "weight_decay": self.wd}
+        return super().state_dict()
 
     def load_state_dict(self, sd):
-        if list(sd["offsets"]) != list(self.offsets) or list(sd["names"]) != list(self.names):
-            raise L.GdlError("DGLTrainer.load_state_dict: the checkpoint's parameter layout differs from this model's")
-        kind = sd.get("optimizer", "sgd")  # (checkpoints written before the optimizer switch are SGD's)
-        if kind != self.optimizer:
-            raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint holds {kind!r} state, this trainer runs "
-                             f"{self.optimizer!r}")
-        state = self._opt_state()
-        for k, v in state.items():
-            v.copy_(sd[k].to(self.device))
-        self.lr, self.steps = float(sd["lr"]), int(sd["steps"])
+        super().load_state_dict(sd)
         if self.reducer is not None:  # the model's parameters alias the arena: whatever rank 0 loaded is the truth
             # (the step count too: the Adam bias corrections are derived from it; and the learning rate)
             hp = torch.tensor([self.lr, float(self.steps)], dtype=torch.float64, device=self.device)
-            self.reducer.sync_state([self.params] + list(state.values()) + self._replica_buffers() + [hp])
+            self.reducer.sync_state([self.params] + list(self._opt_state().values()) + self._replica_buffers() + [hp])
             self.lr, self.steps = float(hp[0].item()), int(hp[1].item())
-
-    def close(self):
-        """Releases what the trainer owns outside PyTorch's allocator: the optimizer descriptor and, for
-        comm_backend="abi", the RCCL communicator (ncclCommDestroy).  Idempotent; also run by __del__."""
-        if getattr(self, "reducer", None) is not None:
-            self.reducer.close()
-        if getattr(self, "opt", None):
-            self.lib.gdl_optim_destroy(self.opt)
-            self.opt = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ setup per batch shape
     def _prepare(self, spec, image):
@@ -369,13 +463,6 @@ class DGLTrainer:
             eng.set_params([p.data for p in net.parameters()], [b.running_mean for b in bns],
                            [b.running_var for b in bns], [b.num_batches_tracked for b in bns])
 
-    def _check_label(self, label):
-        """The loss kernels index logits by label: require the reference's dtype and shape (a class index outside
-        [0, n) raises a device assert in the reference; here the loss kernel skips the sample and poisons the loss)."""
-        if label.dtype != torch.int64 or label.dim() != 1 or label.shape[0] != self.B or label.device != self.device:
-            raise L.GdlError(f"DGLTrainer: label must be an int64 [B={self.B}] tensor on {self.device}, got "
-                             f"{label.dtype} {tuple(label.shape)} on {label.device}")
-
     # ------------------------------------------------------------------ the step
     def step(self, spec, image, label):
         """spec [B,F,T'] float, image [B,3,T,H,W] float, label [B] int64 -- all resident on the device."""
@@ -406,7 +493,6 @@ class DGLTrainer:
         audio = spec.unsqueeze(1)  # main_dgl.py:100
         label = label.contiguous()
         B, n = self.B, self.n_classes
-        nf = self.nf
         self._mark(main, "start")
         ev = main.record_event()
         self.s_a.wait_event(ev)
@@ -417,7 +503,6 @@ class DGLTrainer:
         early = (dgl and self.head in ("concat", "sum") and n <= 512 and self.early_backward is not False
                  and (self.dv == 512 or (self.head == "concat" and self.dv in (768, 1024))))
         red = self.reducer
-        gv, ga = self.gviews[nf + 60:nf + 60 + self.nv], self.gviews[nf:nf + 60]
         if early:
             pv = self.pviews
             if self.head == "concat":  # fc_out [n][512 + dv] + one bias
@@ -434,25 +519,7 @@ class DGLTrainer:
                 L.call("gdl_head_uni_dfeat", L.ptr(self.fa), wa, ldw, ba, L.ptr(label), self.alpha, L.ptr(self.dfa), B, n,
                        self.s_a.cuda_stream)
             # (host order: both forwards are enqueued before either backward, so neither chain waits for the host)
-            with torch.cuda.stream(self.s_v):
-                if red is None:
-                    self.eng_v.backward(gv, dfeat=self.dfv)
-                else:
-                    self.eng_v.backward(gv, dfeat=self.dfv, phase=1)
-            with torch.cuda.stream(self.s_a):
-                if red is None:
-                    self.eng_a.backward(ga, dfeat=self.dfa)
-                else:
-                    # collectives of one communicator run in issue order, identical on every rank
-                    self.eng_a.backward(ga, dfeat=self.dfa, phase=1)
-                    red.launch("audio_l4")
-            if red is not None:
-                with torch.cuda.stream(self.s_v):
-                    red.launch("visual_l4")
-                    self.eng_v.backward(gv, phase=2)
-                with torch.cuda.stream(self.s_a):
-                    self.eng_a.backward(ga, phase=2)
-                    red.launch("audio_rest")
+            self._encoders_backward()
             # the fusion head on the audio stream (= main), behind the audio backward: all three logit sets, the losses, the
             # gradient of fc_out (/ fc_x, fc_y) from loss_f alone; its feature gradients go to scratch (the encoders have theirs)
             main.wait_event(ev_v)
@@ -460,18 +527,7 @@ class DGLTrainer:
             self._head_forward(True, st)
             L.call("gdl_softmax_ce3", L.ptr(self.out), L.ptr(self.out_a), L.ptr(self.out_v), L.ptr(label), 1.0, self.alpha,
                    self.alpha, self.losses.data_ptr(), L.ptr(self.g_f), L.ptr(self.g_a), L.ptr(self.g_v), B, n, st)
-            gvw = self.gviews
-            if self.head == "sum":
-                L.call("gdl_head_sum_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.g_a),
-                       L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(self.dscr_a), L.ptr(self.dscr_v), L.ptr(gvw[0]), L.ptr(gvw[1]),
-                       L.ptr(gvw[2]), L.ptr(gvw[3]), B, n, st)
-            elif self.dv != 512:
-                L.call("gdl_head_concat_xy_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
-                       L.ptr(self.g_f), 0, 0, L.ptr(self.dscr_a), L.ptr(self.dscr_v), L.ptr(gvw[0]), L.ptr(gvw[1]), B, n, 512,
-                       self.dv, st)
-            else:
-                L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
-                       L.ptr(self.g_f), 0, 0, L.ptr(self.dscr_a), L.ptr(self.dscr_v), L.ptr(gvw[0]), L.ptr(gvw[1]), B, n, st)
+            self._dgl_head_backward(self.dscr_a, self.dscr_v, st)
             if red is not None:
                 red.launch("fusion")
                 with torch.cuda.stream(self.s_v):
@@ -494,40 +550,14 @@ class DGLTrainer:
         else:
             L.call("gdl_softmax_ce", L.ptr(self.out), L.ptr(label), 1.0, lp, L.ptr(self.g_f), B, n, st)
         if dgl:
-            # DGL truncation: `out` is computed from detached features (flag 0) and the head gradients of the
-            # unimodal losses are dropped before loss_f.backward() (flag 0)   (main_dgl.py:110-122)
-            if self.head == "film":
-                pv, gv = self.pviews, self.gviews
-                L.call("gdl_head_film_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.hidden),
-                       L.ptr(self.g_a), L.ptr(self.g_v), L.ptr(self.g_f), 0, L.ptr(self.dfa), L.ptr(self.dfv), L.ptr(gv[0]),
-                       L.ptr(gv[1]), L.ptr(gv[2]), L.ptr(gv[3]), B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
-            elif self.head == "gated":
-                fm = self.model.fusion_module
-                L.call("gdl_head_gated_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.hx), L.ptr(self.hy),
-                       L.ptr(fm.fc_x.weight), L.ptr(fm.fc_y.weight), L.ptr(self.pviews[0]), L.ptr(self.g_a), L.ptr(self.g_v),
-                       L.ptr(self.g_f), 0, L.ptr(self.dfa), L.ptr(self.dfv), None, None, None, None, L.ptr(self.gviews[0]),
-                       L.ptr(self.gviews[1]), L.ptr(self.head_ws), B, n, st)
-            elif self.head == "sum":
-                pv, gv = self.pviews, self.gviews
-                L.call("gdl_head_sum_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.g_a),
-                       L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(self.dfa), L.ptr(self.dfv), L.ptr(gv[0]), L.ptr(gv[1]),
-                       L.ptr(gv[2]), L.ptr(gv[3]), B, n, st)
-            elif self.dv != 512:  # 512 + num_features wide fc_out (the Swin composition)
-                L.call("gdl_head_concat_xy_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.pviews[0]), L.ptr(self.g_a),
-                       L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(self.dfa), L.ptr(self.dfv), L.ptr(self.gviews[0]),
-                       L.ptr(self.gviews[1]), B, n, 512, self.dv, st)
-            else:
-                L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.pviews[0]), L.ptr(self.g_a),
-                       L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(self.dfa), L.ptr(self.dfv), L.ptr(self.gviews[0]),
-                       L.ptr(self.gviews[1]), B, n, st)
+            self._dgl_head_backward(self.dfa, self.dfv, st)
         else:  # BASELINE config 1: one CE loss (main.py:161-175) through the head into both encoders
             # Only the feature gradients stand between the head and the encoder backwards.  Without a process group the head's
             # parameter gradients follow behind the junction event, on this stream (= the audio chain, the shorter one) in front
             # of the audio backward; the visual chain, the critical path, starts as soon as dfa / dfv exist.  Same kernels, same
             # numbers.  With a process group the fusion bucket's collective is launched at the junction: everything first.
-            self._joint_head_backward(st, True, self.reducer is not None)
+            self._joint_head_backward(st, True, red is not None)
         self._mark(main, "head_done")
-        red = self.reducer
         if red is not None:
             red.launch("fusion")
         ev2 = main.record_event()
@@ -535,57 +565,63 @@ class DGLTrainer:
         self.s_v.wait_event(ev2)
         if not dgl and red is None:
             self._joint_head_backward(st, False, True)
+        self._encoders_backward()
+        if red is not None:
+            with torch.cuda.stream(self.s_v):
+                red.launch("visual_rest")
+        self._finish_step(main, st)
+
+    def _encoders_backward(self):
+        """Both encoders' backward from self.dfa / self.dfv, the visual one (the critical path) enqueued first.  Data parallel:
+        each in two phases so that the layer4 bucket (75 % of the bytes) is exchanged while layer3 .. stem are still being
+        differentiated.  Collectives of one communicator run in issue order, identical on every rank: audio before visual (the
+        audio passes are the shorter ones) -- audio_l4, visual_l4, audio_rest here; `visual_rest` is the caller's to launch (the
+        early form puts `fusion` in front of it)."""
+        red, nf = self.reducer, self.nf
         gv, ga = self.gviews[nf + 60:nf + 60 + self.nv], self.gviews[nf:nf + 60]
         if red is None:
             with torch.cuda.stream(self.s_v):
                 self.eng_v.backward(gv, dfeat=self.dfv)
             with torch.cuda.stream(self.s_a):
                 self.eng_a.backward(ga, dfeat=self.dfa)
-        else:
-            # Data parallel: each encoder's backward in two phases so that the layer4 bucket (75 % of the bytes) is
-            # exchanged while layer3 .. stem are still being differentiated.  Collectives of one communicator run in
-            # issue order, identical on every rank: audio before visual (the audio passes are the shorter ones).
-            with torch.cuda.stream(self.s_v):
-                self.eng_v.backward(gv, dfeat=self.dfv, phase=1)
-            with torch.cuda.stream(self.s_a):
-                self.eng_a.backward(ga, dfeat=self.dfa, phase=1)
-                red.launch("audio_l4")
-            with torch.cuda.stream(self.s_v):
-                red.launch("visual_l4")
-                self.eng_v.backward(gv, phase=2)
-            with torch.cuda.stream(self.s_a):
-                self.eng_a.backward(ga, phase=2)
-                red.launch("audio_rest")
-            with torch.cuda.stream(self.s_v):
-                red.launch("visual_rest")
-        self._finish_step(main, st)
+            return
+        with torch.cuda.stream(self.s_v):
+            self.eng_v.backward(gv, dfeat=self.dfv, phase=1)
+        with torch.cuda.stream(self.s_a):
+            self.eng_a.backward(ga, dfeat=self.dfa, phase=1)
+            red.launch("audio_l4")
+        with torch.cuda.stream(self.s_v):
+            red.launch("visual_l4")
+            self.eng_v.backward(gv, phase=2)
+        with torch.cuda.stream(self.s_a):
+            self.eng_a.backward(ga, phase=2)
+            red.launch("audio_rest")
 
-    def _finish_step(self, main, st):
-        """Joins the chains (and the collectives), then gradient statistics + clip + the optimizer's update on `main`."""
-        red = self.reducer
-        main.wait_stream(self.s_a)
-        main.wait_stream(self.s_v)
-        if red is not None:
-            red.wait_all()
-        self._mark(main, "bwd_done")
-        gs = 1.0 / self.world
-        L.call("gdl_optim_grad_stats", self.opt, L.ptr(self.grads), self.max_norm, gs, L.ptr(self.stats),
-               L.ptr(self.opt_ws), self.opt_ws_bytes, st)
-        if self.optimizer == "sgd":
-            L.call("gdl_optim_sgd_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.momentum),
-                   L.ptr(self.stats), gs, self.lr, self.mu, self.wd, st)
-        elif self.optimizer == "Adam":
-            L.call("gdl_optim_adamw_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.exp_avg),
-                   L.ptr(self.exp_avg_sq), L.ptr(self.stats), gs, self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, self.wd,
-                   self.steps + 1, st)
+    def _dgl_head_backward(self, dfa, dfv, st):
+        """The DGL step's head backward; the feature gradients go to `dfa` / `dfv`.  DGL truncation: `out` is computed from
+        detached features (flag 0) and the head gradients of the unimodal losses are dropped before loss_f.backward() (flag 0)
+        (main_dgl.py:110-122)."""
+        pv, gv, B, n = self.pviews, self.gviews, self.B, self.n_classes
+        if self.head == "film":
+            L.call("gdl_head_film_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.hidden),
+                   L.ptr(self.g_a), L.ptr(self.g_v), L.ptr(self.g_f), 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]),
+                   L.ptr(gv[1]), L.ptr(gv[2]), L.ptr(gv[3]), B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
+        elif self.head == "gated":
+            fm = self.model.fusion_module
+            L.call("gdl_head_gated_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.hx), L.ptr(self.hy),
+                   L.ptr(fm.fc_x.weight), L.ptr(fm.fc_y.weight), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
+                   L.ptr(self.g_f), 0, L.ptr(dfa), L.ptr(dfv), None, None, None, None, L.ptr(gv[0]), L.ptr(gv[1]),
+                   L.ptr(self.head_ws), B, n, st)
+        elif self.head == "sum":
+            L.call("gdl_head_sum_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.g_a),
+                   L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]), L.ptr(gv[1]),
+                   L.ptr(gv[2]), L.ptr(gv[3]), B, n, st)
+        elif self.dv != 512:  # 512 + num_features wide fc_out (the Swin composition)
+            L.call("gdl_head_concat_xy_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
+                   L.ptr(self.g_f), 0, 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]), L.ptr(gv[1]), B, n, 512, self.dv, st)
         else:
-            L.call("gdl_optim_adagrad_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.state_sum),
-                   L.ptr(self.stats), gs, self.lr, ADAGRAD_EPS, self.wd, self.steps + 1, st)
-        self._mark(main, "end")
-        if self.stats_log is not None and self.stats_log_pos is not None and self.stats_log_pos < self.stats_log.shape[0]:
-            self.stats_log[self.stats_log_pos].copy_(self.stats[:2], non_blocking=True)
-            self.stats_log_pos += 1
-        self.steps += 1
+            L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
+                   L.ptr(self.g_f), 0, 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]), L.ptr(gv[1]), B, n, st)
 
     def _joint_head_backward(self, st, feat, par):
         """The joint step's head backward from self.g_f: `feat` -- dfa / dfv; `par` -- the gradients of every head tensor."""
@@ -635,12 +671,6 @@ class DGLTrainer:
             L.call("gdl_head_concat_fwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[1]), L.ptr(self.out), oa, ov,
                    B, n, st)
 
-    def _mark(self, stream, name):
-        if self.phase_events is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(stream)
-            self.phase_events.append((name, e))
-
     # ------------------------------------------------------------------ validation (main_dgl.py:168-222)
     def valid(self, batches):
         """The reference's valid(): eval-mode forward (BatchNorm running statistics) of every (spec, image, label)
@@ -679,25 +709,10 @@ class DGLTrainer:
     # ------------------------------------------------------------------ results (host sync)
     def read(self):
         """Synchronises and returns the quantities the reference prints / logs per step."""
-        torch.cuda.synchronize(self.device)
-        s = self.stats.cpu().numpy()
+        r = self._read_stats((self.eng_a, self.eng_v))
         ls = self.losses.cpu().numpy()
-        nseg = len(self.names)
-        r = {"loss_f": float(ls[0]), "loss_a": float(ls[1]), "loss_v": float(ls[2]), "total_norm": float(s[0]),
-             "clip_coef": float(s[1]), "audio_grad_sum": float(s[2]), "visual_grad_sum": float(s[3]),
-             "grad_norm": dict(zip(self.names, s[4:4 + nseg].tolist())),
-             "grad_absmean": dict(zip(self.names, s[4 + nseg:4 + 2 * nseg].tolist())),
-             "out": self.out.cpu().numpy()}
+        r.update(loss_f=float(ls[0]), loss_a=float(ls[1]), loss_v=float(ls[2]), out=self.out.cpu().numpy())
         if self.mode == "dgl":
             r["out_a"] = self.out_a.cpu().numpy()
             r["out_v"] = self.out_v.cpu().numpy()
-        # a diverged BatchNorm (statistics beyond the fixed-point headroom, csrc/bnacc.h) must be as loud as the reference's
-        # inf / NaN: ReLU turns the NaN statistics' outputs into zeros, so the logits alone may look sane
-        bad = sum(e.bn_overflow() for e in (self.eng_a, self.eng_v) if e is not None and hasattr(e, "bn_overflow"))
-        if bad:
-            raise FloatingPointError(f"gdl: the statistics of {bad} BatchNorm layer(s) overflowed in the last training forward "
-                                     "(activations of mean magnitude beyond 8192: the run has diverged)")
         return r
-
-    def grad(self, name):
-        return self.gviews[self.names.index(name)]

@@ -12,24 +12,22 @@ The flat arena is [classifier.weight, classifier.bias | the encoder's 60 tensors
 or 2 (visual), so `audio_grad_sum` / `visual_grad_sum` are the existing statistics and the absent one reads 0.0.  The
 `fusion_module` the reference still constructs in these modes gets no gradient: it stays outside the arena, untouched.
 """
-import ctypes
-
 import torch
 
 from . import _lib as L
 from .encoder import EncoderEngine
-from .trainer import ADAGRAD_INITIAL_ACCUMULATOR, DEFAULT_WEIGHT_DECAY, OPTIMIZERS, DGLTrainer, _chain_streams
+from .trainer import ArenaTrainer
 
 
-class UnimodalTrainer(DGLTrainer):
-    """A class of its own beside DGLTrainer (whose step it does not share); what it inherits is the part that does not know
-    the model: the optimizer state and its checkpoint (`state_dict` / `load_state_dict`), the statistics + clip + update tail
-    of the step, `grad(name)` and `close()`."""
+class UnimodalTrainer(ArenaTrainer):
+    """The arenas, the optimizer state and its checkpoint, the statistics + clip + update tail of the step, `grad(name)` and
+    `close()` are ArenaTrainer's; here: the 62-tensor list, the step in front of that tail, valid() and read()."""
+
+    _script = "main.py"
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=None, max_norm=40.0, dtype=None, optimizer="sgd",
                  process_group=None):
-        if optimizer not in OPTIMIZERS:
-            raise ValueError(f"UnimodalTrainer: optimizer must be one of {OPTIMIZERS} (main.py --optimizer), got {optimizer!r}")
+        self._check_optimizer(optimizer)
         if process_group is not None:
             raise L.GdlError("UnimodalTrainer: data-parallel runs (process_group) are not built for the unimodal baselines")
         modality = getattr(model, "modality", None)
@@ -37,73 +35,30 @@ class UnimodalTrainer(DGLTrainer):
             raise L.GdlError("UnimodalTrainer: modality='full' has both encoders -- use gdl.DGLTrainer (mode='dgl' or 'joint')")
         if modality not in ("audio", "visual"):
             raise L.GdlError(f"UnimodalTrainer: model.modality must be 'audio' or 'visual', got {modality!r}")
-        self.optimizer = optimizer
         self.modality = modality
         self.mode = "unimodal"
         net = getattr(model, modality + "_net")
         cls = getattr(model, modality + "_classifier")
-        self.device = cls.weight.device
-        if self.device.type != "cuda":
+        device = cls.weight.device
+        if device.type != "cuda":
             raise L.GdlError("UnimodalTrainer: the model must live on an MI355X (cuda) device; there is no CPU path")
         if hasattr(net, "cfg") and hasattr(net, "num_features"):
             raise L.GdlError("UnimodalTrainer: the Swin branch as the only modality is not built (ResNet18 encoders only)")
         if tuple(cls.weight.shape[1:]) != (512,) or cls.weight.shape[0] > 512:
             raise L.GdlError("UnimodalTrainer: the classifier must be Linear(512, n_classes <= 512)")
-        self.lib = L.load()
         self.model, self.net = model, net
-        self.lr, self.mu, self.max_norm = float(lr), float(momentum), float(max_norm)
-        self.wd = float(DEFAULT_WEIGHT_DECAY[optimizer] if weight_decay is None else weight_decay)
         self.dtype = dtype if dtype is not None else net.gdl_dtype
         self.n_classes = cls.weight.shape[0]
-        self.reducer, self.world, self.pg = None, 1, None
         named = [(modality + "_classifier.weight", cls.weight), (modality + "_classifier.bias", cls.bias)]
         named += [(modality + "_net." + n, p) for n, p in net.named_parameters()]
         if len(named) != 62:
             raise L.GdlError("UnimodalTrainer: the encoder must be the ResNet18 mirror (60 tensors)")
         self.nf = 2
-        self.names = [n for n, _ in named]
-        offs, o = [0], 0
-        for _, p in named:
-            o += p.numel()
-            offs.append(o)
-        self.offsets, self.total = offs, o
         group = [0, 0] + [1 if modality == "audio" else 2] * 60
-        self.params = torch.empty(o, device=self.device)
-        self.grads = torch.zeros(o, device=self.device)
-        self.momentum = self.exp_avg = self.exp_avg_sq = self.state_sum = None
-        if optimizer == "sgd":
-            self.momentum = torch.zeros(o, device=self.device)
-        elif optimizer == "Adam":
-            self.exp_avg = torch.zeros(o, device=self.device)
-            self.exp_avg_sq = torch.zeros(o, device=self.device)
-        else:
-            self.state_sum = torch.full((o,), ADAGRAD_INITIAL_ACCUMULATOR, device=self.device)
-        self.pviews, self.gviews = [], []
-        for i, (_, p) in enumerate(named):
-            v = self.params[offs[i]:offs[i + 1]].view(p.shape)
-            v.copy_(p.data)
-            p.data = v  # the module now aliases the arena: state_dict / eval see the trained weights
-            self.pviews.append(v)
-            self.gviews.append(self.grads[offs[i]:offs[i + 1]].view(p.shape))
-        h = ctypes.c_void_p()
-        L.call("gdl_optim_create", ctypes.byref(h), (ctypes.c_int64 * len(offs))(*offs), (ctypes.c_int32 * len(group))(*group),
-               len(group))
-        self.opt = h
-        self.opt_ws_bytes = self.lib.gdl_optim_workspace_bytes(h)
-        self.opt_ws = torch.empty(max(self.opt_ws_bytes, 8), dtype=torch.uint8, device=self.device)
-        L.call("gdl_optim_bind_workspace", self.opt, L.ptr(self.opt_ws), self.opt_ws_bytes, L.cur_stream())
-        self.stats = torch.zeros(self.lib.gdl_optim_stats_len(h), device=self.device)
+        super().__init__(named, group, device, optimizer, lr, momentum, weight_decay, max_norm)
         self.losses = torch.zeros(1, device=self.device)
-        # the process-wide chain streams (gdl.trainer._chain_streams: never a new one per trainer)
-        self.s_a, self.s_v = _chain_streams(self.device)
         self.chain, self.lane = (self.s_a, self.s_v) if modality == "audio" else (self.s_v, self.s_a)
         self.eng = None
-        self.steps = 0
-        self.phase_events = None
-        self.stats_log = self.stats_log_pos = None
-
-    def _replica_buffers(self):
-        return []
 
     # ------------------------------------------------------------------ setup per batch shape
     def _input(self, spec, image):
@@ -133,11 +88,6 @@ class UnimodalTrainer(DGLTrainer):
         bns = self.net._bn_layers()
         self.eng.set_params([p.data for p in self.net.parameters()], [b.running_mean for b in bns],
                             [b.running_var for b in bns], [b.num_batches_tracked for b in bns])
-
-    def _check_label(self, label):
-        if label.dtype != torch.int64 or label.dim() != 1 or label.shape[0] != self.B or label.device != self.device:
-            raise L.GdlError(f"UnimodalTrainer: label must be an int64 [B={self.B}] tensor on {self.device}, got "
-                             f"{label.dtype} {tuple(label.shape)} on {label.device}")
 
     # ------------------------------------------------------------------ the step
     def step(self, spec, image, label):
@@ -199,18 +149,7 @@ class UnimodalTrainer(DGLTrainer):
     # ------------------------------------------------------------------ results (host sync)
     def read(self):
         """Synchronises and returns the quantities the reference prints / logs per step (its three losses are one)."""
-        torch.cuda.synchronize(self.device)
-        s = self.stats.cpu().numpy()
+        r = self._read_stats((self.eng,))
         loss = float(self.losses.cpu().numpy()[0])
-        nseg = len(self.names)
-        r = {"loss_f": loss, "loss_a": loss, "loss_v": loss, "total_norm": float(s[0]), "clip_coef": float(s[1]),
-             "audio_grad_sum": float(s[2]), "visual_grad_sum": float(s[3]),
-             "grad_norm": dict(zip(self.names, s[4:4 + nseg].tolist())),
-             "grad_absmean": dict(zip(self.names, s[4 + nseg:4 + 2 * nseg].tolist())),
-             "out": self.out.cpu().numpy()}
-        # (a diverged BatchNorm must be as loud as the reference's inf / NaN: DGLTrainer.read)
-        bad = self.eng.bn_overflow() if self.eng is not None else 0
-        if bad:
-            raise FloatingPointError(f"gdl: the statistics of {bad} BatchNorm layer(s) overflowed in the last training forward "
-                                     "(activations of mean magnitude beyond 8192: the run has diverged)")
+        r.update(loss_f=loss, loss_a=loss, loss_v=loss, out=self.out.cpu().numpy())
         return r

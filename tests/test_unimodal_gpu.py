@@ -130,6 +130,18 @@ def test_fused_call_equals_three_calls(B, n, scale):
         assert torch.equal(_bits(a), _bits(c))
 
 
+@pytest.mark.parametrize("scale", [1.0, 4.0])
+@pytest.mark.parametrize("B,n", SIZES)
+def test_fused_call_df_equals_uni_dfeat(B, n, scale):
+    """gdl_head_cls_ce and gdl_head_uni_dfeat (512 features, row pitch 512) run one per-sample body (csrc/head_body.h): the
+    feature gradients of the two launches are the same bits."""
+    f, W, b, _, lab = _head_case(B, n)
+    df_uni = torch.full((B, 512), NAN, device=DEV)
+    L.call("gdl_head_uni_dfeat", L.ptr(f), L.ptr(W), 512, L.ptr(b), L.ptr(lab), scale, L.ptr(df_uni), B, n, L.cur_stream())
+    df = _cls_ce(f, W, b, lab, scale)[3]
+    assert torch.equal(_bits(df), _bits(df_uni))
+
+
 # ------------------------------------------------------------------ the step
 _STATE = {}
 _TINY = dict(dataset="CREMAD", n_classes=6, spec_hw=[65, 47], frames=2, image_hw=[64, 64], batch=4, seed=0, lr=2e-3)
