@@ -265,6 +265,16 @@ int gdl_head_uni_dfeat_w(const float* f, const float* Wp, int ldw, const float* 
     GDL_REQUIRE(f && Wp && bp && labels && df && B > 0 && n_classes > 0 && ldw >= width, "head_uni_dfeat_w: bad arguments");
     return head_uni_dfeat(f, Wp, ldw, bp, labels, scale, df, B, n_classes, width, (hipStream_t)stream);
 }
+size_t gdl_head_uni_scores_workspace_bytes(void) { return 16; }
+int gdl_head_uni_scores(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba,
+                        const float* bv, float bias_scale, const int64_t* labels, float* prob, float* scores, int B,
+                        int n_classes, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(fa && fv && Wa && Wv && ba && bv && labels && prob && scores && ws && B > 0 && n_classes > 0 && ldw >= 512,
+                "head_uni_scores: bad arguments");
+    GDL_REQUIRE(ws_bytes >= gdl_head_uni_scores_workspace_bytes() && ((uintptr_t)ws & 3) == 0,
+                "head_uni_scores: workspace of %zu bytes, 4-byte aligned", gdl_head_uni_scores_workspace_bytes());
+    return head_uni_scores(fa, fv, Wa, Wv, ldw, ba, bv, bias_scale, labels, prob, scores, B, n_classes, ws, (hipStream_t)stream);
+}
 int gdl_head_cls_fwd(const float* f, const float* W, const float* b, float* out, int B, int n_classes, int width, void* stream) {
     GDL_REQUIRE(f && W && b && out && B > 0 && n_classes > 0, "head_cls_fwd: bad arguments");
     GDL_REQUIRE(width == 512, "head_cls_fwd: feature width %d (the classifier is built for 512)", width);

@@ -446,6 +446,78 @@ int head_uni_dfeat(const float* f, const float* Wp, int ldw, const float* bp, co
     return GDL_OK;
 }
 
+// ---------------------------------------------------------------- the unimodal scores of OGM / OGM-GE (main.py:286-295)
+// u_a = fa Wa^T + bias_scale ba, u_v = fv Wv^T + bias_scale bv;  prob[b] = {softmax(u_a[b])[label_b], softmax(u_v[b])[label_b]};
+// scores = {sum_b prob[b][0], sum_b prob[b][1]}.  grid = B, a sample per block: the classes go round the 16 waves two at a time
+// (head_dot2), wave 0 / wave 1 then take the audio / visual softmax.  The block that draws the last ticket adds the B
+// probabilities of each modality in sample order (one thread each: a fixed order, no float atomics) and hands the ticket
+// counter back at zero.  A label outside [0, n) makes the sample's probabilities -- and with them the scores -- NaN.
+__global__ __launch_bounds__(1024) void head_uni_scores_kernel(const float* __restrict__ fa, const float* __restrict__ fv,
+                                                              const float* __restrict__ Wa, const float* __restrict__ Wv, int ldw,
+                                                              const float* __restrict__ ba, const float* __restrict__ bv,
+                                                              float bias_scale, const int64_t* __restrict__ labels,
+                                                              float* prob, float* __restrict__ scores,
+                                                              unsigned int* __restrict__ ticket, int B, int n) {
+    __shared__ float lg[2][HB_MAXN];
+    __shared__ unsigned int last;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const float* W = m ? Wv : Wa;
+        const float* bias = m ? bv : ba;
+        float fr[8];
+        head_load_feat<8>((m ? fv : fa) + (size_t)b * 512, lane, fr);
+        for (int j = wave; j < n; j += 2 * HB_NW) {
+            const int j2 = j + HB_NW;
+            float pa, pb;
+            head_dot2<8>(W + (size_t)j * ldw, W + (size_t)(j2 < n ? j2 : j) * ldw, fr, lane, pa, pb);
+            if (lane == 0) {
+                lg[m][j] = pa + bias_scale * bias[j];
+                if (j2 < n) lg[m][j2] = pb + bias_scale * bias[j2];
+            }
+        }
+    }
+    __syncthreads();
+    if (wave < 2) {
+        const float* l = lg[wave];
+        float mx = -INFINITY;
+        for (int j = lane; j < n; j += 64) mx = fmaxf(mx, l[j]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        float se = 0.f;
+        for (int j = lane; j < n; j += 64) se += expf(l[j] - mx);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+        const long lab64 = (long)labels[b];
+        if (lane == 0) prob[(size_t)b * 2 + wave] = (lab64 >= 0 && lab64 < n) ? expf(l[lab64] - mx) / se : __builtin_nanf("");
+    }
+    __threadfence();  // the two probabilities are visible device-wide before the ticket is drawn
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == (unsigned int)(B - 1);
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    if (threadIdx.x < 2) {
+        const volatile float* pr = prob;
+        float s = 0.f;
+        for (int i = 0; i < B; ++i) s += pr[(size_t)i * 2 + threadIdx.x];
+        scores[threadIdx.x] = s;
+    }
+    if (threadIdx.x == 0) *ticket = 0u;
+}
+int head_uni_scores(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
+                    float bias_scale, const int64_t* labels, float* prob, float* scores, int B, int n, void* ws, hipStream_t st) {
+    GDL_REQUIRE(n <= HB_MAXN, "head_uni_scores: at most %d classes", HB_MAXN);
+    ProfScope prof("gdl::head_uni_scores_kernel", PROF_HBM, st, (double)B * 1024 * 4.0 + (double)n * 1024 * 4.0);
+    hipLaunchKernelGGL(head_uni_scores_kernel, dim3(B), dim3(1024), 0, st, fa, fv, Wa, Wv, ldw, ba, bv, bias_scale, labels, prob,
+                       scores, (unsigned int*)ws, B, n);
+    GDL_CHECK_LAUNCH("head_uni_scores_kernel");
+    return GDL_OK;
+}
+
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
 
 // grid = (B, 2): which = 0 -> hx = x W1^T + b1, 1 -> hy = y W2^T + b2.  Waves own outputs j = wave, wave+4, ..

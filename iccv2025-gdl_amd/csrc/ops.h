@@ -161,6 +161,8 @@ int avgpool_bwd(int dtype, const float* dfeat, void* dx, int B, int T, int HW, i
 // head.hip
 int head_uni_dfeat(const float* f, const float* Wp, int ldw, const float* bp, const int64_t* labels, float scale, float* df, int B,
                    int n, int width, hipStream_t st);
+int head_uni_scores(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
+                    float bias_scale, const int64_t* labels, float* prob, float* scores, int B, int n, void* ws, hipStream_t st);
 // head_cls.hip: the Linear(512, n) classifier of the unimodal baselines
 int head_cls_fwd(const float* f, const float* W, const float* b, float* out, int B, int n, hipStream_t st);
 int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B, int n, hipStream_t st);

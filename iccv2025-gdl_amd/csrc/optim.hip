@@ -29,6 +29,11 @@ struct gdl_optim {
     std::vector<unsigned char> h_tables;  // the first three, concatenated as they sit in the workspace
     size_t off_segrange = 0, off_segnumel = 0, off_partial = 0;
     const void* bound_ws = nullptr;
+    // gradient modulation (OGM / OGM-GE): per-segment marks 0 = untouched, 1 = audio, 2 = visual, kept on the host and uploaded
+    // into the head of the caller's modulation workspace by gdl_optim_modulate_bind: mod_ws = [marks int32[nseg] | per-chunk sums]
+    std::vector<int32_t> marks;
+    size_t off_modpartial = 0;
+    const void* bound_mod_ws = nullptr;
 };
 
 namespace gdl {
@@ -277,6 +282,186 @@ __global__ __launch_bounds__(256) void adagrad_kernel(float* __restrict__ p, flo
     }
 }
 
+// ---------------------------------------------------------------- OGM / OGM-GE gradient modulation (main.py:286-330)
+// Between the clip and the update, for every marked segment (the 4-D tensors of an encoder) with c its modality's coefficient:
+//   OGM:    g <- (g k) c                       k = clip_coef * grad_scale, what the update kernels multiply by
+//   OGM_GE: g <- (g k) c + sigma z             sigma = std(g k) + 1e-8 (unbiased, of the whole clipped tensor), z ~ N(0, 1)
+// Unmarked segments get g k, as the update kernels would have written it; those then run with stats = NULL, grad_scale = 1.
+// Three launches: the per-chunk sum of the marked chunks (the statistics pass has the sum of squares), one block that turns
+// the scores into the two coefficients and the sums into the per-segment sigma, and the chunked in-place pass.
+
+// Philox4x32-10 (Salmon et al., SC'11): counter c, key k.
+struct Philox4 {
+    uint32_t v[4];
+};
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+// Box-Muller on a pair of words, u(w) = ((w >> 8) + 0.5) 2^-24: r = sqrt(-2 ln u(wa)), theta = 2 pi u(wb).  (w >> 8) + 0.5 has
+// 25 significant bits, so the radius takes its logarithm in double: a float u rounds to 1 next to it, where ln u is all error.
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {
+    const float r = (float)sqrt(-2.0 * log(((double)(wa >> 8) + 0.5) * 0x1p-24));
+    const float th = 6.283185307179586f * (((float)(wb >> 8) + 0.5f) * 0x1p-24f);
+    float sn, cs;
+    sincosf(th, &sn, &cs);
+    z0 = r * cs;
+    z1 = r * sn;
+}
+
+// the four normals of the aligned group of arena elements 4 q .. 4 q + 3 at `step`: element i takes z[i & 3]
+__device__ __forceinline__ void noise4(int64_t q, int64_t step, uint32_t seed_lo, uint32_t seed_hi, float (&z)[4]) {
+    const Philox4 w = philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)step, (uint32_t)((uint64_t)step >> 32),
+                                    seed_lo, seed_hi);
+    box_muller(w.v[0], w.v[1], z[0], z[1]);
+    box_muller(w.v[2], w.v[3], z[2], z[3]);
+}
+
+// sum of g over each chunk of a marked segment (float per thread over at most 32 elements, then double, in a fixed order)
+__global__ __launch_bounds__(256) void mod_sum_kernel(const float* __restrict__ g, const ChunkDesc* __restrict__ chunks,
+                                                      const int32_t* __restrict__ marks, double* __restrict__ partial) {
+    __shared__ double sh[256];
+    const ChunkDesc c = chunks[blockIdx.x];
+    if (marks[c.seg] == 0) return;
+    const float* p = g + c.start;
+    float s = 0.f;
+    const int head = min(c.len, (int)((4 - (c.start & 3)) & 3));
+    const int nv = (c.len - head) >> 2;
+    const float4* p4 = (const float4*)(p + head);
+    for (int i = threadIdx.x; i < nv; i += 256) {
+        const float4 v = p4[i];
+        s += (v.x + v.y) + (v.z + v.w);
+    }
+    {  // the at most 3 + 3 elements around the aligned middle
+        const int t = threadIdx.x, tail = c.len - head - 4 * nv;
+        if (t < head) s += p[t];
+        else if (t - head < tail) s += p[head + 4 * nv + (t - head)];
+    }
+    sh[threadIdx.x] = (double)s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+
+// mstats[0] score_a, [1] score_v, [2] ratio_v, [3] coeff_a, [4] coeff_v, [5..7] 0, [8 + s] sigma of segment s (0 where unmarked
+// or without noise).  segsum: the statistics pass's per-segment {sum g^2, sum |g|} of the unscaled gradient.
+constexpr int MOD_STATS_HEAD = 8;
+__global__ __launch_bounds__(FIN_NT) void mod_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ segrange,
+                                                        const double* __restrict__ segnumel, const int32_t* __restrict__ marks,
+                                                        const double* __restrict__ segsum, int nseg,
+                                                        const float* __restrict__ stats, float grad_scale,
+                                                        const float* __restrict__ scores, float alpha, int noise,
+                                                        float* __restrict__ mstats) {
+    const float k = stats[1] * grad_scale;  // the update kernels' factor, in their arithmetic
+    const int grp16 = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+    for (int s = grp16; s < nseg; s += FIN_NT / 16) {  // (the 16-lane fold of grad_stats_final_kernel)
+        float sigma = 0.f;
+        if (noise && marks[s] != 0) {
+            const int first = segrange[s * 4 + 0], cnt = segrange[s * 4 + 1];
+            double a = 0.0;
+            for (int j = l16; j < cnt; j += 16) a += partial[first + j];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) a += __shfl_down(a, o, 16);
+            const double n = segnumel[s];
+            double var = (segsum[s * 2 + 0] - a * a / n) / (n - 1.0);
+            if (var < 0.0) var = 0.0;
+            sigma = (float)((double)k * sqrt(var) + 1e-8);
+        }
+        if (l16 == 0) mstats[MOD_STATS_HEAD + s] = sigma;
+    }
+    if (threadIdx.x == 0) {
+        // ratio_v = score_v / score_a; the side that leads is slowed by 1 - tanh(alpha * its ratio) (= 2 / (e^2x + 1): no
+        // cancellation), the other keeps 1; ratio_v == 1 takes the audio branch (main.py:296-301)
+        const double sa = (double)scores[0], sv = (double)scores[1];
+        const double rv = sv / sa;
+        double ca = 1.0, cv = 1.0;
+        if (rv > 1.0)
+            cv = 2.0 / (exp(2.0 * (double)alpha * rv) + 1.0);
+        else
+            ca = 2.0 / (exp(2.0 * (double)alpha * (1.0 / rv)) + 1.0);
+        mstats[0] = scores[0];
+        mstats[1] = scores[1];
+        mstats[2] = (float)rv;
+        mstats[3] = (float)ca;
+        mstats[4] = (float)cv;
+        mstats[5] = mstats[6] = mstats[7] = 0.f;
+    }
+}
+
+template <bool NOISE>
+__device__ __forceinline__ float mod1(float g, float k, float c, float sigma, float z) {
+    const float gk = g * k;
+    return NOISE ? fmaf(sigma, z, gk * c) : gk * c;
+}
+
+// one chunk per block, in place; element i of the arena takes the normal z[i & 3] of its aligned group of four
+template <bool NOISE>
+__global__ __launch_bounds__(256) void modulate_kernel(float* __restrict__ g, const ChunkDesc* __restrict__ chunks,
+                                                       const int32_t* __restrict__ marks, const float* __restrict__ stats,
+                                                       float grad_scale, const float* __restrict__ mstats, uint32_t seed_lo,
+                                                       uint32_t seed_hi, int64_t step) {
+    const ChunkDesc c = chunks[blockIdx.x];
+    const float k = stats[1] * grad_scale;
+    const int mark = marks[c.seg];
+    float* p = g + c.start;
+    const int head = min(c.len, (int)((4 - (c.start & 3)) & 3));
+    const int nv = (c.len - head) >> 2;
+    float4* p4 = (float4*)(p + head);
+    if (mark == 0) {  // g k, stored only where the update kernels would have stored it
+        if (k == 1.f) return;
+        for (int i = threadIdx.x; i < nv; i += 256) {
+            float4 v = p4[i];
+            v.x *= k;
+            v.y *= k;
+            v.z *= k;
+            v.w *= k;
+            p4[i] = v;
+        }
+        const int t = threadIdx.x, tail = c.len - head - 4 * nv;
+        if (t < head) p[t] *= k;
+        else if (t - head < tail) p[head + 4 * nv + (t - head)] *= k;
+        return;
+    }
+    const float coef = mstats[2 + mark];  // [3] audio, [4] visual
+    const float sigma = NOISE ? mstats[MOD_STATS_HEAD + c.seg] : 0.f;
+    const int64_t q0 = (c.start + head) >> 2;
+    for (int i = threadIdx.x; i < nv; i += 256) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (NOISE) noise4(q0 + i, step, seed_lo, seed_hi, z);
+        float4 v = p4[i];
+        v.x = mod1<NOISE>(v.x, k, coef, sigma, z[0]);
+        v.y = mod1<NOISE>(v.y, k, coef, sigma, z[1]);
+        v.z = mod1<NOISE>(v.z, k, coef, sigma, z[2]);
+        v.w = mod1<NOISE>(v.w, k, coef, sigma, z[3]);
+        p4[i] = v;
+    }
+    {
+        const int t = threadIdx.x, tail = c.len - head - 4 * nv;
+        const int j = t < head ? t : (t - head < tail ? head + 4 * nv + (t - head) : -1);
+        if (j >= 0) {
+            const int64_t e = c.start + j;
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (NOISE) noise4(e >> 2, step, seed_lo, seed_hi, z);
+            const int l = (int)(e & 3);
+            p[j] = mod1<NOISE>(p[j], k, coef, sigma, l == 0 ? z[0] : (l == 1 ? z[1] : (l == 2 ? z[2] : z[3])));
+        }
+    }
+}
+
 // grid of the streaming update kernels: one float4 per thread, grid-stride beyond 4096 blocks of 256
 static int64_t update_blocks(int64_t total) {
     int64_t blocks = ((total >> 2) + 255) / 256;
@@ -383,6 +568,74 @@ int gdl_optim_grad_stats(gdl_optim_t* o, const float* grads, float max_norm, flo
                        (const int32_t*)(w + o->off_segrange), (const double*)(w + o->off_segnumel), o->nseg, max_norm, grad_scale,
                        stats, segsum);
     GDL_CHECK_LAUNCH("grad_stats_final_kernel");
+    return GDL_OK;
+}
+
+size_t gdl_optim_modulate_workspace_bytes(const gdl_optim_t* o) {
+    if (!o) return 0;
+    return (((size_t)o->nseg * sizeof(int32_t) + 255) & ~(size_t)255) + (size_t)o->nchunks * sizeof(double);
+}
+
+int gdl_optim_modulate_stats_len(const gdl_optim_t* o) { return o ? MOD_STATS_HEAD + o->nseg : 0; }
+
+int gdl_optim_modulate_bind(gdl_optim_t* o, const int32_t* seg_mark, void* mod_ws, size_t mod_ws_bytes, void* stream) {
+    GDL_REQUIRE(o && seg_mark && mod_ws, "optim_modulate_bind: null argument");
+    if (mod_ws_bytes < gdl_optim_modulate_workspace_bytes(o)) {
+        set_error("optim_modulate_bind: workspace %zu < %zu", mod_ws_bytes, gdl_optim_modulate_workspace_bytes(o));
+        return GDL_ERR_WORKSPACE;
+    }
+    GDL_REQUIRE(((uintptr_t)mod_ws & 15) == 0, "optim_modulate_bind: workspace must be 16-byte aligned");
+    for (int s = 0; s < o->nseg; ++s) {
+        GDL_REQUIRE(seg_mark[s] >= 0 && seg_mark[s] <= 2, "optim_modulate_bind: mark %d of segment %d (0 untouched, 1 audio, 2 visual)",
+                    seg_mark[s], s);
+        // (the unbiased standard deviation divides by n - 1)
+        GDL_REQUIRE(seg_mark[s] == 0 || o->offs[s + 1] - o->offs[s] >= 2, "optim_modulate_bind: marked segment %d has fewer than 2 elements", s);
+    }
+    o->marks.assign(seg_mark, seg_mark + o->nseg);
+    o->off_modpartial = ((size_t)o->nseg * sizeof(int32_t) + 255) & ~(size_t)255;
+    hipError_t he = hipMemcpyAsync(mod_ws, o->marks.data(), o->marks.size() * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (he != hipSuccess) return check_hip(he, "optim_modulate_bind: mark upload");
+    o->bound_mod_ws = mod_ws;
+    return GDL_OK;
+}
+
+int gdl_optim_modulate(gdl_optim_t* o, float* grads, const float* stats, float grad_scale, const float* scores, float alpha,
+                       int noise, int64_t seed, int64_t step, float* mod_stats, const void* ws, void* mod_ws, void* stream) {
+    GDL_REQUIRE(o && grads && stats && scores && mod_stats && ws && mod_ws, "optim_modulate: null argument");
+    GDL_REQUIRE(noise == 0 || noise == 1, "optim_modulate: noise must be 0 (OGM) or 1 (OGM_GE)");
+    GDL_REQUIRE(((uintptr_t)grads & 15) == 0, "optim_modulate: the gradient arena must be 16-byte aligned");
+    GDL_REQUIRE(o->bound_mod_ws == mod_ws && !o->marks.empty(), "optim_modulate: mod_ws is not the workspace gdl_optim_modulate_bind was given");
+    GDL_REQUIRE(o->bound_ws == ws, "optim_modulate: ws is not the workspace gdl_optim_grad_stats last ran on");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* w = (const unsigned char*)ws;
+    const ChunkDesc* chunks = (const ChunkDesc*)w;
+    const int32_t* segrange = (const int32_t*)(w + o->off_segrange);
+    const double* segnumel = (const double*)(w + o->off_segnumel);
+    const double* segsum = (const double*)(w + o->off_partial) + (size_t)o->nchunks * 2;
+    const int32_t* marks = (const int32_t*)mod_ws;
+    double* partial = (double*)((unsigned char*)mod_ws + o->off_modpartial);
+    int64_t marked = 0;
+    for (int s = 0; s < o->nseg; ++s)
+        if (o->marks[s]) marked += o->offs[s + 1] - o->offs[s];
+    if (noise) {
+        ProfScope prof("gdl::mod_sum_kernel", PROF_HBM, st, (double)marked * 4.0);
+        hipLaunchKernelGGL(mod_sum_kernel, dim3(o->nchunks), dim3(256), 0, st, (const float*)grads, chunks, marks, partial);
+        GDL_CHECK_LAUNCH("mod_sum_kernel");
+    }
+    hipLaunchKernelGGL(mod_final_kernel, dim3(1), dim3(FIN_NT), 0, st, (const double*)partial, segrange, segnumel, marks, segsum,
+                       o->nseg, stats, grad_scale, scores, alpha, noise, mod_stats);
+    GDL_CHECK_LAUNCH("mod_final_kernel");
+    {
+        // (marked elements read and written; the unmarked ones only where clip_coef * grad_scale != 1, not charged -- as sgd_kernel)
+        ProfScope prof(noise ? "gdl::modulate_kernel<true>" : "gdl::modulate_kernel<false>", PROF_HBM, st, (double)marked * 8.0);
+        if (noise)
+            hipLaunchKernelGGL(modulate_kernel<true>, dim3(o->nchunks), dim3(256), 0, st, grads, chunks, marks, stats, grad_scale,
+                               (const float*)mod_stats, (uint32_t)((uint64_t)seed & 0xffffffffu), (uint32_t)((uint64_t)seed >> 32), step);
+        else
+            hipLaunchKernelGGL(modulate_kernel<false>, dim3(o->nchunks), dim3(256), 0, st, grads, chunks, marks, stats, grad_scale,
+                               (const float*)mod_stats, 0u, 0u, step);
+        GDL_CHECK_LAUNCH("modulate_kernel");
+    }
     return GDL_OK;
 }
 

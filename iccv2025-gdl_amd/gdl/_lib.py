@@ -100,6 +100,8 @@ SIGNATURES = {
     "gdl_avgpool_bwd": ("i", "ipp" + "iiii" + "p"),
     "gdl_head_uni_dfeat": ("i", "pp" + "i" + "pp" + "f" + "p" + "ii" + "p"),
     "gdl_head_uni_dfeat_w": ("i", "pp" + "i" + "pp" + "f" + "p" + "iii" + "p"),
+    "gdl_head_uni_scores_workspace_bytes": ("z", ""),
+    "gdl_head_uni_scores": ("i", "pppp" + "i" + "pp" + "f" + "ppp" + "ii" + "pz" + "p"),
     "gdl_head_cls_fwd": ("i", "pppp" + "iii" + "p"),
     "gdl_head_cls_bwd": ("i", "pppppp" + "iii" + "p"),
     "gdl_head_cls_ce": ("i", "pppp" + "f" + "pppp" + "iii" + "p"),
@@ -133,6 +135,10 @@ SIGNATURES = {
     "gdl_optim_sgd_step": ("i", "ppppp" + "ffff" + "p"),
     "gdl_optim_adamw_step": ("i", "pppppp" + "f" + "ddddd" + "l" + "p"),
     "gdl_optim_adagrad_step": ("i", "ppppp" + "f" + "ddd" + "l" + "p"),
+    "gdl_optim_modulate_workspace_bytes": ("z", "p"),
+    "gdl_optim_modulate_stats_len": ("i", "p"),
+    "gdl_optim_modulate_bind": ("i", "pppzp"),
+    "gdl_optim_modulate": ("i", "pppfpf" + "ill" + "ppp" + "p"),
     "gdl_encoder_create": ("i", "piiiiii"),
     "gdl_encoder_destroy": (None, "p"),
     "gdl_encoder_side_stream": ("i", "pi"),

@@ -21,6 +21,9 @@ every data-parallel run):
   audio encoder backward (stream A)  ||  visual encoder backward (stream V)
       [+ per-bucket RCCL all-reduce as soon as a bucket is final]
   grad statistics, clip + SGD as above
+Joint step with modulation="OGM" / "OGM_GE" (main.py:286-330; concat and sum heads): gdl_head_uni_scores behind the head forward
+(the unimodal scores, on the device), and gdl_optim_modulate between the statistics and the update -- the convolution weight
+gradients of both encoders become (g k) c [+ sigma z] in the arena, the update takes the arena as it stands.
 
 ArenaTrainer below is what such a runner is before it knows its model (the flat arenas, the optimizer state and its checkpoint,
 the chain streams, the statistics + clip + update tail); DGLTrainer is the step above on it, gdl.unimodal.UnimodalTrainer the
@@ -80,6 +83,9 @@ ADAM_BETAS = (0.9, 0.999)
 ADAM_EPS = 1e-8
 ADAGRAD_EPS = 1e-10
 ADAGRAD_INITIAL_ACCUMULATOR = 0.0
+# main.py's `--modulation` (:286-330): "Normal" = none; "OGM" = the encoder whose unimodal score leads has its convolution weight
+# gradients scaled by 1 - tanh(alpha * ratio); "OGM_GE" = the same plus N(0, std(g) + 1e-8) noise on both encoders' (CVPR 2022)
+MODULATIONS = ("Normal", "OGM", "OGM_GE")
 
 _CHAIN_STREAMS = {}
 
@@ -167,6 +173,27 @@ class ArenaTrainer:
         # (total norm, clip coefficient) into the next row, device to device on the step's stream
         self.stats_log = None
         self.stats_log_pos = None
+        # gradient modulation (a subclass calls `_setup_modulation`): None = the step launches none of its kernels
+        self._mod = None
+        self._mod_now = False
+
+    def _setup_modulation(self, marks, noise, alpha, seed):
+        """OGM / OGM-GE over the gradient arena: marks[i] = 0 (untouched), 1 (audio) or 2 (visual) per arena tensor; `noise` =
+        the GE term.  The subclass leaves {score_a, score_v} in `self.mod_scores` before `_finish_step` of a step it has set
+        `self._mod_now` for."""
+        lib = self.lib
+        nb = lib.gdl_optim_modulate_workspace_bytes(self.opt)
+        self.mod_ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.device)
+        self.mod_stats = torch.zeros(lib.gdl_optim_modulate_stats_len(self.opt), device=self.device)
+        self.mod_scores = torch.zeros(2, device=self.device)
+        L.call("gdl_optim_modulate_bind", self.opt, (ctypes.c_int32 * len(marks))(*marks), L.ptr(self.mod_ws), nb, L.cur_stream())
+        self._mod = (int(bool(noise)), float(alpha), int(seed))
+
+    @classmethod
+    def _check_modulation(cls, modulation):
+        """(like `_check_optimizer`: before the model is touched)"""
+        if modulation not in MODULATIONS:
+            raise ValueError(f"{cls.__name__}: modulation must be one of {MODULATIONS} (main.py --modulation), got {modulation!r}")
 
     def _opt_state(self):
         """{name: arena} of the chosen optimizer's state: momentum (sgd), exp_avg + exp_avg_sq (Adam), state_sum (AdaGrad)."""
@@ -225,16 +252,24 @@ class ArenaTrainer:
         gs = 1.0 / self.world
         L.call("gdl_optim_grad_stats", self.opt, L.ptr(self.grads), self.max_norm, gs, L.ptr(self.stats),
                L.ptr(self.opt_ws), self.opt_ws_bytes, st)
+        stats = L.ptr(self.stats)
+        if self._mod is not None and self._mod_now:
+            # main.py:286-330, between the clip and optimizer.step(): the clipped and modulated gradient is written to the arena,
+            # the update then takes it as it stands (stats = NULL, grad_scale = 1); the noise counter is the step count
+            noise, alpha, seed = self._mod
+            L.call("gdl_optim_modulate", self.opt, L.ptr(self.grads), stats, gs, L.ptr(self.mod_scores), alpha, noise, seed,
+                   self.steps, L.ptr(self.mod_stats), L.ptr(self.opt_ws), L.ptr(self.mod_ws), st)
+            stats, gs = None, 1.0
         if self.optimizer == "sgd":
             L.call("gdl_optim_sgd_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.momentum),
-                   L.ptr(self.stats), gs, self.lr, self.mu, self.wd, st)
+                   stats, gs, self.lr, self.mu, self.wd, st)
         elif self.optimizer == "Adam":
             L.call("gdl_optim_adamw_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.exp_avg),
-                   L.ptr(self.exp_avg_sq), L.ptr(self.stats), gs, self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, self.wd,
+                   L.ptr(self.exp_avg_sq), stats, gs, self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, self.wd,
                    self.steps + 1, st)
         else:
             L.call("gdl_optim_adagrad_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.state_sum),
-                   L.ptr(self.stats), gs, self.lr, ADAGRAD_EPS, self.wd, self.steps + 1, st)
+                   stats, gs, self.lr, ADAGRAD_EPS, self.wd, self.steps + 1, st)
         self._mark(main, "end")
         if self.stats_log is not None and self.stats_log_pos is not None and self.stats_log_pos < self.stats_log.shape[0]:
             self.stats_log[self.stats_log_pos].copy_(self.stats[:2], non_blocking=True)
@@ -269,12 +304,18 @@ class ArenaTrainer:
 
 class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
-                 process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd"):
+                 process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
+                 modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
-        None = the reference's value for that optimizer (DEFAULT_WEIGHT_DECAY); `momentum` applies to "sgd" only."""
+        None = the reference's value for that optimizer (DEFAULT_WEIGHT_DECAY); `momentum` applies to "sgd" only.
+        modulation: main.py's `--modulation` for the joint step (mode="joint", concat or sum head, no process group): "Normal",
+        "OGM" or "OGM_GE" (MODULATIONS); `alpha` is then main.py's `--alpha` (its scripts use 0.8), the modulation runs while
+        modulation_starts <= self.epoch <= modulation_ends (the caller sets `epoch`), and `seed` keys OGM_GE's noise, a function
+        of (seed, step count, arena position) alone."""
         self._check_optimizer(optimizer)
+        self._check_modulation(modulation)
         self.model = model
         self.mode = mode
         self.alpha = float(alpha)
@@ -343,8 +384,29 @@ class DGLTrainer(ArenaTrainer):
             raise L.GdlError("DGLTrainer: the Swin visual branch is built for the concat DGL head")
         if not self.vis_swin and self.nv != 60:
             raise L.GdlError("DGLTrainer: visual_net must be the ResNet18 mirror or the SwinTransformer mirror")
+        self.modulation = modulation
+        self.modulation_starts, self.modulation_ends = int(modulation_starts), int(modulation_ends)
+        self.seed = int(seed)
+        self.epoch = 0  # the caller sets it per epoch: the modulation's window (main.py:290)
+        if modulation != "Normal":
+            if not self.joint:  # main_dgl.py parses --modulation and never reads it: not silently ignored here
+                raise L.GdlError("DGLTrainer: gradient modulation belongs to the joint step (mode=\"joint\", main.py); "
+                                 "main_dgl.py's step has none")
+            if self.vis_swin:
+                raise L.GdlError("DGLTrainer: gradient modulation is not built for the Swin visual branch")
+            if self.head not in ("concat", "sum"):
+                raise L.GdlError(f"DGLTrainer: OGM's unimodal logits are defined for the concat and sum heads, not for {self.head!r}")
+            if process_group is not None:
+                raise L.GdlError("DGLTrainer: gradient modulation with a process group is not supported (the scores would need "
+                                 "a collective of their own)")
+            if not 0 <= self.seed < 2 ** 63:
+                raise ValueError("DGLTrainer: seed must be in [0, 2**63)")
         group = [0] * nf + [1] * 60 + [2] * self.nv
         super().__init__(named, group, device, optimizer, lr, momentum, weight_decay, max_norm)
+        if modulation != "Normal":  # every 4-D tensor (convolution weight) of the two encoders; BatchNorm and the head untouched
+            self._setup_modulation([g if p.dim() == 4 else 0 for g, (_, p) in zip(group, named)], modulation == "OGM_GE",
+                                   self.alpha, self.seed)
+            self.score_ws = torch.zeros(max(self.lib.gdl_head_uni_scores_workspace_bytes(), 4), dtype=torch.uint8, device=device)
         offs = self.offsets
         # all-reduce buckets (ranges of the flat gradient arena).  layer4 = the last 15 tensors of an encoder, 8.4 M
         # of its 11.2 M parameters, is final right after the first two blocks of the backward: its own bucket lets
@@ -387,10 +449,20 @@ class DGLTrainer(ArenaTrainer):
         """In data-parallel mode the BatchNorm buffers are first made rank 0's, so model.state_dict() taken next is the
         reference's replica-0 state."""
         self.sync_replicas()
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.modulation != "Normal":  # (main.py's checkpoints record --modulation and assert on it at load)
+            sd.update(modulation=self.modulation, seed=self.seed)
+        return sd
 
     def load_state_dict(self, sd):
+        kind = sd.get("modulation", "Normal")
+        if kind != self.modulation:
+            raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint was trained with modulation {kind!r}, this trainer "
+                             f"runs {self.modulation!r}")
         super().load_state_dict(sd)
+        if self._mod is not None:  # the noise continues the checkpoint's stream: its key, and the step count loaded above
+            self.seed = int(sd.get("seed", self.seed))
+            self._mod = self._mod[:2] + (self.seed,)
         if self.reducer is not None:  # the model's parameters alias the arena: whatever rank 0 loaded is the truth
             # (the step count too: the Adam bias corrections are derived from it; and the learning rate)
             hp = torch.tensor([self.lr, float(self.steps)], dtype=torch.float64, device=self.device)
@@ -452,6 +524,10 @@ class DGLTrainer(ArenaTrainer):
             self.head_ws = torch.empty(2 * B * 512, device=d)
         self.out, self.out_a, self.out_v = (torch.empty((B, n), device=d) for _ in range(3))
         self.g_f, self.g_a, self.g_v = (torch.empty((B, n), device=d) for _ in range(3))
+        if self._mod is not None:
+            if n > 512:
+                raise L.GdlError("DGLTrainer: gradient modulation handles at most 512 classes")
+            self.mod_prob = torch.empty((B, 2), device=d)  # softmax(out_a)[label], softmax(out_v)[label] per sample
         self.B = B
 
     def _bind(self):
@@ -563,6 +639,17 @@ class DGLTrainer(ArenaTrainer):
         ev2 = main.record_event()
         self.s_a.wait_event(ev2)
         self.s_v.wait_event(ev2)
+        self._mod_now = (self._mod is not None and self.modulation_starts <= self.epoch <= self.modulation_ends)
+        if self._mod_now:
+            # OGM's unimodal scores from the pooled features and the head's current parameters (main.py:286-295), behind the
+            # head forward on its stream (= the audio chain, the shorter one): the visual backward is not kept waiting
+            pv = self.pviews
+            if self.head == "concat":  # out_a = a W[:, :512]^T + b / 2, out_v = v W[:, 512:]^T + b / 2
+                wa, wv, ldw, ba, bv, bs = L.ptr(pv[0]), pv[0].data_ptr() + 512 * 4, 1024, L.ptr(pv[1]), L.ptr(pv[1]), 0.5
+            else:  # out_a = fc_x(a), out_v = fc_y(v)
+                wa, wv, ldw, ba, bv, bs = L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3]), 1.0
+            L.call("gdl_head_uni_scores", L.ptr(self.fa), L.ptr(self.fv), wa, wv, ldw, ba, bv, bs, L.ptr(label),
+                   L.ptr(self.mod_prob), L.ptr(self.mod_scores), B, n, L.ptr(self.score_ws), self.score_ws.numel(), st)
         if not dgl and red is None:
             self._joint_head_backward(st, False, True)
         self._encoders_backward()
@@ -715,4 +802,7 @@ class DGLTrainer(ArenaTrainer):
         if self.mode == "dgl":
             r["out_a"] = self.out_a.cpu().numpy()
             r["out_v"] = self.out_v.cpu().numpy()
+        if self._mod is not None and self._mod_now:  # the last step was modulated (the statistics above are the unmodulated ones)
+            m = self.mod_stats[:5].cpu().numpy()
+            r["ogm"] = dict(score_a=float(m[0]), score_v=float(m[1]), ratio_v=float(m[2]), coeff_a=float(m[3]), coeff_v=float(m[4]))
         return r

@@ -283,6 +283,18 @@ GDL_API int gdl_head_uni_dfeat(const float* f, const float* Wp, int ldw, const f
  * Wp = W + 512 with ldw = 512 + 768); df bit-identical to gdl_head_concat_xy_fwd + gdl_softmax_ce3 + gdl_head_concat_xy_bwd. */
 GDL_API int gdl_head_uni_dfeat_w(const float* f, const float* Wp, int ldw, const float* bp, const int64_t* labels, float scale,
                                  float* df, int B, int n_classes, int width, void* stream);
+/* The unimodal scores of OGM / OGM-GE gradient modulation (main.py:286-295, the published definitions) in ONE launch:
+ *   u_a = fa Wa^T + bias_scale*ba,  u_v = fv Wv^T + bias_scale*bv      (fa, fv [B][512]; Wa, Wv: row stride ldw floats)
+ *   prob[b] = {softmax(u_a[b])[labels[b]], softmax(u_v[b])[labels[b]]}   ([B][2], device)
+ *   scores  = {sum_b prob[b][0], sum_b prob[b][1]}                       ([2], device; added in sample order, no float atomics)
+ * ConcatFusion: Wa = W, Wv = W + 512, ldw 1024, ba = bv = fc_out.bias, bias_scale 0.5; SumFusion: fc_x / fc_y, ldw 512, their
+ * biases, bias_scale 1.  n_classes <= 512.  A label outside [0, n) makes the sample's probabilities and both scores NaN.
+ * `ws` (gdl_head_uni_scores_workspace_bytes, 4-byte aligned) holds a ticket counter: the caller zeroes it ONCE, every launch
+ * that runs to its end leaves it zero again.  Launches sharing one `ws` must be ordered on one stream. */
+GDL_API size_t gdl_head_uni_scores_workspace_bytes(void);
+GDL_API int gdl_head_uni_scores(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba,
+                                const float* bv, float bias_scale, const int64_t* labels, float* prob, float* scores, int B,
+                                int n_classes, void* ws, size_t ws_bytes, void* stream);
 /* The classifier of the unimodal baselines (AVClassifier_DGL with modality 'audio' / 'visual', basic_model.py:46-59, 88-122:
  * nn.Linear(512, n_classes) on the pooled features of the one encoder, trained by main.py's single CrossEntropyLoss).
  * float32: f [B][width], W [n][width], b [n]; width must be 512 and n_classes <= 512 (other sizes: GDL_ERR_ARG).
@@ -483,6 +495,31 @@ GDL_API int gdl_optim_adamw_step(gdl_optim_t* o, float* params, float* grads, fl
                                  double weight_decay, int64_t step, void* stream);
 GDL_API int gdl_optim_adagrad_step(gdl_optim_t* o, float* params, float* grads, float* state_sum, const float* stats,
                                    float grad_scale, double lr, double eps, double weight_decay, int64_t step, void* stream);
+/* OGM / OGM-GE gradient modulation (main.py:286-330), between gdl_optim_grad_stats and the update, over the gradient arena in
+ * place.  seg_mark[nseg] (int32, host): 0 = untouched, 1 = audio-modulated, 2 = visual-modulated (the 4-D tensors of the two
+ * encoders); a marked segment has at least 2 elements.  With k = clip_coef*grad_scale (stats[1] of the statistics pass that
+ * ran on `ws` just before) and `scores` = {score_a, score_v} on the device (gdl_head_uni_scores):
+ *   ratio_v = score_v/score_a;  ratio_v > 1: coeff_v = 1 - tanh(alpha*ratio_v), coeff_a = 1;
+ *                               otherwise:   coeff_a = 1 - tanh(alpha/ratio_v), coeff_v = 1
+ *   marked segment of modality m:  g <- (g*k)*coeff_m                  (noise = 0: OGM)
+ *                                  g <- (g*k)*coeff_m + sigma*z        (noise = 1: OGM_GE; BOTH modalities get the noise)
+ *     sigma = k*std(g) + 1e-8, std the unbiased standard deviation of the whole tensor (in double from the statistics pass's
+ *     sum of squares and a sum pass of this call);  z ~ N(0, 1) from Philox4x32-10, key = (seed low, seed high 32 bits),
+ *     counter = (i >> 2, 0, step, 0) for arena element i, which takes normal i & 3 of the Box-Muller pairs of words (0, 1)
+ *     and (2, 3), u(w) = ((w >> 8) + 0.5) * 2^-24, r = sqrt(-2 ln u(w0)), theta = 2 pi u(w1): a function of (seed, step, i)
+ *     alone -- not of the launch geometry, the rank or the segment table.
+ *   unmarked segment:  g <- g*k, as the update kernels store it.
+ * Call the update that follows with stats = NULL and grad_scale = 1.  Everything stays on the device, nothing synchronises.
+ * mod_stats (gdl_optim_modulate_stats_len = 8 + nseg floats, device): {score_a, score_v, ratio_v, coeff_a, coeff_v, 0, 0, 0,
+ * sigma of every segment (0 where unmarked or noise = 0)}.  `mod_ws` (gdl_optim_modulate_workspace_bytes, 16-byte aligned,
+ * caller-owned) is separate from `ws`, whose size does not change; gdl_optim_modulate_bind uploads the marks into it (ordered on
+ * `stream`) and must have been called with the same pointer. */
+GDL_API size_t gdl_optim_modulate_workspace_bytes(const gdl_optim_t* o);
+GDL_API int gdl_optim_modulate_stats_len(const gdl_optim_t* o);
+GDL_API int gdl_optim_modulate_bind(gdl_optim_t* o, const int32_t* seg_mark, void* mod_ws, size_t mod_ws_bytes, void* stream);
+GDL_API int gdl_optim_modulate(gdl_optim_t* o, float* grads, const float* stats, float grad_scale, const float* scores,
+                               float alpha, int noise, int64_t seed, int64_t step, float* mod_stats, const void* ws,
+                               void* mod_ws, void* stream);
 
 /* ------------------------------------------------------------------ ResNet18 encoder engine
  * `resnet18(modality, args)` / ResNet.forward (backbone.py:75-201, 255-257) plus the
