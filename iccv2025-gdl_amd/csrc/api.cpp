@@ -292,6 +292,19 @@ int gdl_head_cls_ce(const float* f, const float* W, const float* b, const int64_
     GDL_REQUIRE(width == 512, "head_cls_ce: feature width %d (the classifier is built for 512)", width);
     return head_cls_ce(f, W, b, labels, scale, out, loss, dlogits, df, B, n_classes, (hipStream_t)stream);
 }
+size_t gdl_head_mtl_ce_workspace_bytes(int B) { return head_mtl_ce_ws_bytes(B); }
+int gdl_head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
+                    int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out, float* out_a, float* out_v,
+                    float* losses, float* g_f, float* g_a, float* g_v, float* dfa, float* dfv, int B, int n_classes, void* ws,
+                    size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(fa && fv && Wa && Wv && ba && bv && labels && out && out_a && out_v && losses && g_f && g_a && g_v && dfa && dfv &&
+                    ws && B > 0 && n_classes > 0 && ldw >= 512,
+                "head_mtl_ce: bad arguments");
+    GDL_REQUIRE(ws_bytes >= head_mtl_ce_ws_bytes(B) && ((uintptr_t)ws & 3) == 0, "head_mtl_ce: workspace of %zu bytes, 4-byte aligned",
+                head_mtl_ce_ws_bytes(B));
+    return head_mtl_ce(fa, fv, Wa, Wv, ldw, ba, bv, sum_bias != 0, labels, scale_u, fused_reaches != 0, out, out_a, out_v, losses, g_f,
+                       g_a, g_v, dfa, dfv, B, n_classes, ws, (hipStream_t)stream);
+}
 int gdl_head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out,
                         float* y_out, int B, int n_classes, void* stream) {
     GDL_REQUIRE(x && y && W && b && out && B > 0 && n_classes > 0, "head_concat_fwd: bad arguments");

@@ -168,6 +168,11 @@ int head_cls_fwd(const float* f, const float* W, const float* b, float* out, int
 int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B, int n, hipStream_t st);
 int head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out, float* loss,
                 float* dlogits, float* df, int B, int n, hipStream_t st);
+// head_mtl.hip: the one-launch junction of the step whose fused loss reaches the encoders (concat / sum DGL head, un-detached)
+size_t head_mtl_ce_ws_bytes(int B);
+int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
+                int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out, float* out_a, float* out_v,
+                float* losses, float* g_f, float* g_a, float* g_v, float* dfa, float* dfv, int B, int n, void* ws, hipStream_t st);
 int head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out, float* y_out,
                     int B, int n, hipStream_t st);
 int head_concat_bwd(const float* x, const float* y, const float* W, const float* g_x_out, const float* g_y_out,

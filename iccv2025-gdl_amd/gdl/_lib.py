@@ -105,6 +105,8 @@ SIGNATURES = {
     "gdl_head_cls_fwd": ("i", "pppp" + "iii" + "p"),
     "gdl_head_cls_bwd": ("i", "pppppp" + "iii" + "p"),
     "gdl_head_cls_ce": ("i", "pppp" + "f" + "pppp" + "iii" + "p"),
+    "gdl_head_mtl_ce_workspace_bytes": ("z", "i"),
+    "gdl_head_mtl_ce": ("i", "pppp" + "i" + "pp" + "i" + "p" + "fi" + "ppp" + "p" + "ppp" + "pp" + "ii" + "pz" + "p"),
     "gdl_head_concat_fwd": ("i", "ppppppp" + "ii" + "p"),
     "gdl_head_concat_bwd": ("i", "pppppp" + "ii" + "pppp" + "ii" + "p"),
     "gdl_softmax_ce": ("i", "ppf" + "pp" + "ii" + "p"),

@@ -25,6 +25,15 @@ Joint step with modulation="OGM" / "OGM_GE" (main.py:286-330; concat and sum hea
 (the unimodal scores, on the device), and gdl_optim_modulate between the statistics and the update -- the convolution weight
 gradients of both encoders become (g k) c [+ sigma z] in the arena, the update takes the arena as it stands.
 
+DGL ablations (mode="dgl"; `detach_fused`, `drop_head_uni`): DGL is two truncations of one three-loss step -- the fused logits are
+detached (main_dgl.py:100-108, the .detach() inside every *_DGL head) and the unimodal losses' gradients in the fusion module are
+dropped (:114-122).  drop_head_uni=False keeps the latter (the head kernels' uni_in_dw = 1; every form above still applies).
+detach_fused=False (concat / sum head, ResNet18 encoders) lets loss_f reach the encoders: an encoder's feature gradient then
+needs both encoders' features, so the step is the junction form with ONE launch at the junction,
+  both forwards -> gdl_head_mtl_ce (three logit sets, three losses, their gradients, dfa / dfv) -> event -> both backward chains,
+and the head's parameter gradients behind the junction on the audio stream.  Both off = the multi-task baseline
+loss_f + gamma (loss_a + loss_v) of main.py:177 under plain autograd (alpha = the scripts' --gamma).
+
 ArenaTrainer below is what such a runner is before it knows its model (the flat arenas, the optimizer state and its checkpoint,
 the chain streams, the statistics + clip + update tail); DGLTrainer is the step above on it, gdl.unimodal.UnimodalTrainer the
 one-encoder step.
@@ -305,7 +314,7 @@ class ArenaTrainer:
 class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
-                 modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0):
+                 modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
@@ -313,7 +322,11 @@ class DGLTrainer(ArenaTrainer):
         modulation: main.py's `--modulation` for the joint step (mode="joint", concat or sum head, no process group): "Normal",
         "OGM" or "OGM_GE" (MODULATIONS); `alpha` is then main.py's `--alpha` (its scripts use 0.8), the modulation runs while
         modulation_starts <= self.epoch <= modulation_ends (the caller sets `epoch`), and `seed` keys OGM_GE's noise, a function
-        of (seed, step count, arena position) alone."""
+        of (seed, step count, arena position) alone.
+        detach_fused, drop_head_uni: the two gradient truncations DGL is made of (mode="dgl"; the defaults are DGL itself).
+        drop_head_uni=False: the fusion head also learns from the unimodal losses -- the unmodified AVClassifier_DGL under ONE
+        backward of loss_f + alpha (loss_a + loss_v).  detach_fused=False (concat and sum heads): loss_f also reaches the encoders.
+        Both False: the multi-task baseline of main.py:177, `alpha` being the scripts' --gamma."""
         self._check_optimizer(optimizer)
         self._check_modulation(modulation)
         self.model = model
@@ -356,6 +369,14 @@ class DGLTrainer(ArenaTrainer):
         # mode: "dgl" = the step of main_dgl.py; "joint" (or its older name "concat") = the single-loss step of the jointly
         # trained model (main.py:161-175): every head tensor and both encoders learn from CE(out) alone
         self.joint = mode != "dgl"
+        self.detach_fused, self.drop_head_uni = bool(detach_fused), bool(drop_head_uni)
+        self.ablation = not (self.detach_fused and self.drop_head_uni)
+        # tuning aid (A/B, honoured only with GDL_TUNING=1): GDL_MTL_FUSED=0 = the three-launch junction of the detach_fused=False step
+        self.mtl_fused = not (os.environ.get("GDL_TUNING") == "1" and os.environ.get("GDL_MTL_FUSED") == "0")
+        # GatedFusion_DGL's fc_x / fc_y receive a gradient from the unimodal losses once those are kept (drop_head_uni=False):
+        # all six tensors then live in the arena, fc_out behind them (named_parameters() order, as in the joint gated step)
+        gated_all = self.head == "gated" and (self.joint or (mode == "dgl" and not self.drop_head_uni))
+        self._go = 4 if gated_all and not self.joint else 0  # where fc_out sits among the DGL gated step's arena tensors
         self.x_gate = bool(getattr(head, "x_gate", True))
         if self.head == "gated" and not self.x_gate and not self.joint:
             raise L.GdlError("DGLTrainer: GatedFusion_DGL is built for x_gate=True (basic_model.py:38)")
@@ -365,10 +386,10 @@ class DGLTrainer(ArenaTrainer):
         if self.head == "film":
             named = [("fusion_module.fc.weight", head.fc.weight), ("fusion_module.fc.bias", head.fc.bias),
                      ("fusion_module.fc_out.weight", head.fc_out.weight), ("fusion_module.fc_out.bias", head.fc_out.bias)]
-        elif self.head == "sum" or (self.head == "gated" and self.joint):
+        elif self.head == "sum" or gated_all:
             named = [("fusion_module.fc_x.weight", head.fc_x.weight), ("fusion_module.fc_x.bias", head.fc_x.bias),
                      ("fusion_module.fc_y.weight", head.fc_y.weight), ("fusion_module.fc_y.bias", head.fc_y.bias)]
-            if self.head == "gated":  # the joint loss trains all six tensors (named_parameters() order)
+            if self.head == "gated":  # all six tensors are trained (named_parameters() order)
                 named += [("fusion_module.fc_out.weight", head.fc_out.weight), ("fusion_module.fc_out.bias", head.fc_out.bias)]
         else:
             named = [("fusion_module.fc_out.weight", head.fc_out.weight), ("fusion_module.fc_out.bias", head.fc_out.bias)]
@@ -384,6 +405,18 @@ class DGLTrainer(ArenaTrainer):
             raise L.GdlError("DGLTrainer: the Swin visual branch is built for the concat DGL head")
         if not self.vis_swin and self.nv != 60:
             raise L.GdlError("DGLTrainer: visual_net must be the ResNet18 mirror or the SwinTransformer mirror")
+        if self.ablation:
+            if mode != "dgl":  # the joint step has one loss and nothing to truncate: never silently ignored
+                raise L.GdlError("DGLTrainer: detach_fused / drop_head_uni switch the truncations of the DGL step (mode=\"dgl\"); "
+                                 f"the {mode!r} step has none")
+            if self.vis_swin:
+                raise L.GdlError("DGLTrainer: the DGL ablation switches are not built for the Swin visual branch")
+            if process_group is not None:
+                raise L.GdlError("DGLTrainer: the DGL ablation switches with a process group are not supported (the collective "
+                                 "order of their steps has not been validated)")
+            if not self.detach_fused and self.head not in ("concat", "sum"):
+                raise L.GdlError(f"DGLTrainer: detach_fused=False is built for the concat and sum heads, not for {self.head!r} (its "
+                                 "fused path into the features needs kernels of its own)")
         self.modulation = modulation
         self.modulation_starts, self.modulation_ends = int(modulation_starts), int(modulation_ends)
         self.seed = int(seed)
@@ -452,6 +485,8 @@ class DGLTrainer(ArenaTrainer):
         sd = super().state_dict()
         if self.modulation != "Normal":  # (main.py's checkpoints record --modulation and assert on it at load)
             sd.update(modulation=self.modulation, seed=self.seed)
+        if self.ablation:  # (the arena's composition and the step depend on them)
+            sd.update(detach_fused=self.detach_fused, drop_head_uni=self.drop_head_uni)
         return sd
 
     def load_state_dict(self, sd):
@@ -459,6 +494,10 @@ class DGLTrainer(ArenaTrainer):
         if kind != self.modulation:
             raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint was trained with modulation {kind!r}, this trainer "
                              f"runs {self.modulation!r}")
+        sw = (bool(sd.get("detach_fused", True)), bool(sd.get("drop_head_uni", True)))
+        if sw != (self.detach_fused, self.drop_head_uni):
+            raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint was trained with detach_fused={sw[0]}, drop_head_uni={sw[1]}, "
+                             f"this trainer runs detach_fused={self.detach_fused}, drop_head_uni={self.drop_head_uni}")
         super().load_state_dict(sd)
         if self._mod is not None:  # the noise continues the checkpoint's stream: its key, and the step count loaded above
             self.seed = int(sd.get("seed", self.seed))
@@ -524,6 +563,8 @@ class DGLTrainer(ArenaTrainer):
             self.head_ws = torch.empty(2 * B * 512, device=d)
         self.out, self.out_a, self.out_v = (torch.empty((B, n), device=d) for _ in range(3))
         self.g_f, self.g_a, self.g_v = (torch.empty((B, n), device=d) for _ in range(3))
+        if not self.detach_fused:  # gdl_head_mtl_ce's ticket counter and loss terms: zeroed here once, left zero by every launch
+            self.mtl_ws = torch.zeros(self.lib.gdl_head_mtl_ce_workspace_bytes(B), dtype=torch.uint8, device=d)
         if self._mod is not None:
             if n > 512:
                 raise L.GdlError("DGLTrainer: gradient modulation handles at most 512 classes")
@@ -576,7 +617,7 @@ class DGLTrainer(ArenaTrainer):
         # the visual encoder is the critical path (3x the audio work): enqueue it first so the single
         # host thread's ~100 launches per encoder pass do not delay it
         dgl = self.mode == "dgl"
-        early = (dgl and self.head in ("concat", "sum") and n <= 512 and self.early_backward is not False
+        early = (dgl and self.detach_fused and self.head in ("concat", "sum") and n <= 512 and self.early_backward is not False
                  and (self.dv == 512 or (self.head == "concat" and self.dv in (768, 1024))))
         red = self.reducer
         if early:
@@ -618,6 +659,17 @@ class DGLTrainer(ArenaTrainer):
         main.wait_stream(self.s_v)
         self._mark(main, "fwd_done")
         st = main.cuda_stream
+        if dgl and not self.detach_fused:
+            self._mtl_junction(label, st)
+            self._mark(main, "head_done")
+            ev2 = main.record_event()
+            self.s_v.wait_event(ev2)
+            # the head's parameter gradients behind the junction event, on this stream (= the audio chain, the shorter one) in
+            # front of the audio backward, as in the joint step
+            self._dgl_head_backward(None, None, st)
+            self._encoders_backward()
+            self._finish_step(main, st)
+            return
         self._head_forward(dgl, st)
         lp = self.losses.data_ptr()
         if dgl:  # loss_f, alpha*loss_a, alpha*loss_v (main_dgl.py:102-108) in one launch
@@ -684,31 +736,55 @@ class DGLTrainer(ArenaTrainer):
             self.eng_a.backward(ga, phase=2)
             red.launch("audio_rest")
 
-    def _dgl_head_backward(self, dfa, dfv, st):
-        """The DGL step's head backward; the feature gradients go to `dfa` / `dfv`.  DGL truncation: `out` is computed from
-        detached features (flag 0) and the head gradients of the unimodal losses are dropped before loss_f.backward() (flag 0)
-        (main_dgl.py:110-122)."""
-        pv, gv, B, n = self.pviews, self.gviews, self.B, self.n_classes
+    def _mtl_junction(self, label, st):
+        """What stands between the forwards and the backward chains when the fused loss reaches the encoders (concat / sum head):
+        the three logit sets, the three losses, their logit gradients and dfa / dfv -- gdl_head_mtl_ce, ONE launch; beyond its 512
+        classes (or with the tuning aid GDL_MTL_FUSED=0) the three launches it replaces, bit for bit."""
+        pv, B, n = self.pviews, self.B, self.n_classes
+        if self.mtl_fused and n <= 512:
+            if self.head == "concat":  # fc_out [n][1024] + one bias
+                wa, wv, ldw, ba, bv, sb = L.ptr(pv[0]), pv[0].data_ptr() + 512 * 4, 1024, L.ptr(pv[1]), L.ptr(pv[1]), 0
+            else:  # fc_x, fc_y [n][512] with their biases
+                wa, wv, ldw, ba, bv, sb = L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3]), 1
+            L.call("gdl_head_mtl_ce", L.ptr(self.fa), L.ptr(self.fv), wa, wv, ldw, ba, bv, sb, L.ptr(label), self.alpha, 1,
+                   L.ptr(self.out), L.ptr(self.out_a), L.ptr(self.out_v), self.losses.data_ptr(), L.ptr(self.g_f), L.ptr(self.g_a),
+                   L.ptr(self.g_v), L.ptr(self.dfa), L.ptr(self.dfv), B, n, L.ptr(self.mtl_ws), self.mtl_ws.numel(), st)
+            return
+        self._head_forward(True, st)
+        L.call("gdl_softmax_ce3", L.ptr(self.out), L.ptr(self.out_a), L.ptr(self.out_v), L.ptr(label), 1.0, self.alpha,
+               self.alpha, self.losses.data_ptr(), L.ptr(self.g_f), L.ptr(self.g_a), L.ptr(self.g_v), B, n, st)
+        self._dgl_head_backward(self.dfa, self.dfv, st, par=False)
+
+    def _dgl_head_backward(self, dfa, dfv, st, par=True):
+        """The DGL step's head backward; the feature gradients go to `dfa` / `dfv` (None: not computed), `par`: the parameter
+        gradients.  DGL truncation: `out` is computed from detached features (out_reaches_xy = 0) and the head gradients of the
+        unimodal losses are dropped before loss_f.backward() (uni_in_dw = 0) (main_dgl.py:110-122); `detach_fused` /
+        `drop_head_uni` = False lift one or the other."""
+        pv, B, n = self.pviews, self.B, self.n_classes
+        reach, uni = int(not self.detach_fused), int(not self.drop_head_uni)
+        gv = [L.ptr(g) if par else None for g in self.gviews[:self.nf]]
+        dfa, dfv = (L.ptr(dfa), L.ptr(dfv)) if dfa is not None else (None, None)
         if self.head == "film":
             L.call("gdl_head_film_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.hidden),
-                   L.ptr(self.g_a), L.ptr(self.g_v), L.ptr(self.g_f), 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]),
-                   L.ptr(gv[1]), L.ptr(gv[2]), L.ptr(gv[3]), B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
+                   L.ptr(self.g_a), L.ptr(self.g_v), L.ptr(self.g_f), uni, dfa, dfv, gv[0],
+                   gv[1], gv[2], gv[3], B, n, L.ptr(self.head_ws), self.head_ws.numel(), st)
         elif self.head == "gated":
-            fm = self.model.fusion_module
+            fm, go = self.model.fusion_module, self._go
+            d1 = gv[:4] if go else [None] * 4  # fc_x / fc_y: trained by the unimodal losses alone, when those are kept
             L.call("gdl_head_gated_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(self.hx), L.ptr(self.hy),
-                   L.ptr(fm.fc_x.weight), L.ptr(fm.fc_y.weight), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
-                   L.ptr(self.g_f), 0, L.ptr(dfa), L.ptr(dfv), None, None, None, None, L.ptr(gv[0]), L.ptr(gv[1]),
+                   L.ptr(fm.fc_x.weight), L.ptr(fm.fc_y.weight), L.ptr(pv[go]), L.ptr(self.g_a), L.ptr(self.g_v),
+                   L.ptr(self.g_f), uni, dfa, dfv, d1[0], d1[1], d1[2], d1[3], gv[go], gv[go + 1],
                    L.ptr(self.head_ws), B, n, st)
         elif self.head == "sum":
             L.call("gdl_head_sum_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), L.ptr(self.g_a),
-                   L.ptr(self.g_v), L.ptr(self.g_f), 0, 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]), L.ptr(gv[1]),
-                   L.ptr(gv[2]), L.ptr(gv[3]), B, n, st)
+                   L.ptr(self.g_v), L.ptr(self.g_f), reach, uni, dfa, dfv, gv[0], gv[1],
+                   gv[2], gv[3], B, n, st)
         elif self.dv != 512:  # 512 + num_features wide fc_out (the Swin composition)
             L.call("gdl_head_concat_xy_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
-                   L.ptr(self.g_f), 0, 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]), L.ptr(gv[1]), B, n, 512, self.dv, st)
+                   L.ptr(self.g_f), reach, uni, dfa, dfv, gv[0], gv[1], B, n, 512, self.dv, st)
         else:
             L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(self.g_a), L.ptr(self.g_v),
-                   L.ptr(self.g_f), 0, 0, L.ptr(dfa), L.ptr(dfv), L.ptr(gv[0]), L.ptr(gv[1]), B, n, st)
+                   L.ptr(self.g_f), reach, uni, dfa, dfv, gv[0], gv[1], B, n, st)
 
     def _joint_head_backward(self, st, feat, par):
         """The joint step's head backward from self.g_f: `feat` -- dfa / dfv; `par` -- the gradients of every head tensor."""
@@ -746,8 +822,8 @@ class DGLTrainer(ArenaTrainer):
         elif self.head == "gated":  # fusion_modules.py:232-250
             fm = self.model.fusion_module
             L.call("gdl_head_gated_fwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(fm.fc_x.weight), L.ptr(fm.fc_x.bias),
-                   L.ptr(fm.fc_y.weight), L.ptr(fm.fc_y.bias), L.ptr(pv[0]), L.ptr(pv[1]), L.ptr(self.hx), L.ptr(self.hy),
-                   L.ptr(self.out), oa, ov, B, n, st)
+                   L.ptr(fm.fc_y.weight), L.ptr(fm.fc_y.bias), L.ptr(pv[self._go]), L.ptr(pv[self._go + 1]), L.ptr(self.hx),
+                   L.ptr(self.hy), L.ptr(self.out), oa, ov, B, n, st)
         elif self.head == "sum":  # fusion_modules.py:22-30
             L.call("gdl_head_sum_fwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[1]), L.ptr(pv[2]), L.ptr(pv[3]),
                    L.ptr(self.out), oa, ov, B, n, st)

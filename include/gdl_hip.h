@@ -313,6 +313,28 @@ GDL_API int gdl_head_cls_bwd(const float* f, const float* W, const float* g_out,
                              int n_classes, int width, void* stream);
 GDL_API int gdl_head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out,
                             float* loss, float* dlogits, float* df, int B, int n_classes, int width, void* stream);
+/* The junction of the step whose FUSED loss reaches the encoders, in ONE launch: the concat / sum DGL head without its .detach()
+ * (the DGL ablation "no detach" and the multi-task baseline loss_f + gamma (loss_a + loss_v), main.py:177).  float32,
+ * fa, fv [B][512]; Wa, Wv: row stride ldw floats; n_classes <= 512 (more: GDL_ERR_ARG, nothing is launched or touched).
+ *   ConcatFusion_DGL: Wa = W, Wv = W + 512, ldw 1024, ba = bv = fc_out.bias, sum_bias 0 (the one bias serves all three sets);
+ *   SumFusion_DGL:    Wa = fc_x.weight, Wv = fc_y.weight, ldw 512, their biases, sum_bias 1 (`out` carries ba + bv).
+ *   out_a = fa Wa^T + ba,  out_v = fv Wv^T + bv,  out = fa Wa^T + fv Wv^T + bias                      ([B][n] each)
+ *   losses[3] = {CE(out), CE(out_a), CE(out_v)}: unscaled means, as gdl_softmax_ce3 reports them
+ *   g_f = (softmax(out) - onehot)/B,  g_a = scale_u (softmax(out_a) - onehot)/B,  g_v likewise          ([B][n] each)
+ *   dfa = (g_a + fused_reaches g_f) Wa,  dfv = (g_v + fused_reaches g_f) Wv                            ([B][512] each)
+ * The logits, the logit gradients and dfa / dfv are bit-identical to gdl_head_{concat,sum}_fwd + gdl_softmax_ce3(1, scale_u,
+ * scale_u) + gdl_head_{concat,sum}_bwd(out_reaches_xy = fused_reaches)'s dx / dy.  Each loss sums its B per-sample terms in one
+ * fixed order (no floating-point atomics): every output is bit-reproducible from run to run.  A label outside [0, n) gives no
+ * one-hot term and NaN losses, as in gdl_softmax_ce.  The head's parameter gradients are gdl_head_{concat,sum}_bwd's, with
+ * dx = dy = NULL, from g_f / g_a / g_v.
+ * `ws` (gdl_head_mtl_ce_workspace_bytes(B), 4-byte aligned) holds a ticket counter and the 3 B per-sample loss terms: the caller
+ * zeroes it ONCE, every launch that runs to its end leaves the counter zero again.  Launches sharing one `ws` must be ordered
+ * on one stream. */
+GDL_API size_t gdl_head_mtl_ce_workspace_bytes(int B);
+GDL_API int gdl_head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba,
+                            const float* bv, int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out,
+                            float* out_a, float* out_v, float* losses, float* g_f, float* g_a, float* g_v, float* dfa, float* dfv,
+                            int B, int n_classes, void* ws, size_t ws_bytes, void* stream);
 /* The concat head with unequal feature widths, W [n][x_dim + y_dim] (512 audio + 768 Swin features; the reference's
  * ConcatFusion_Swin, fusion_modules.py:79-88, in its DGL form :45-59): same contract as the two calls above. */
 GDL_API int gdl_head_concat_xy_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out,
