@@ -292,6 +292,22 @@ int gdl_head_cls_ce(const float* f, const float* W, const float* b, const int64_
     GDL_REQUIRE(width == 512, "head_cls_ce: feature width %d (the classifier is built for 512)", width);
     return head_cls_ce(f, W, b, labels, scale, out, loss, dlogits, df, B, n_classes, (hipStream_t)stream);
 }
+size_t gdl_feature_diversity_workspace_bytes(int n_img) { return feature_diversity_ws_bytes(n_img); }
+int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int P, int C, float* per_image, float* mean_out,
+                          float* accum, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(map && mean_out && ws, "feature_diversity: null map, mean_out or workspace");
+    GDL_REQUIRE(dt_ok(dtype) && (layout == GDL_LAYOUT_NHWC || layout == GDL_LAYOUT_NCHW), "feature_diversity: dtype %d, layout %d",
+                dtype, layout);
+    GDL_REQUIRE(C == 512, "feature_diversity: built for C = 512 channels (the ResNet18 encoders' final map), got %d", C);
+    GDL_REQUIRE(P >= 1 && P <= 256, "feature_diversity: P = h w must be in [1, 256], got %d", P);
+    GDL_REQUIRE(n_img >= 1, "feature_diversity: n_img must be at least 1, got %d", n_img);
+    GDL_REQUIRE(!(layout == GDL_LAYOUT_NCHW && dtype != GDL_F32), "feature_diversity: the NCHW layout is float32 only (bf16 maps are NHWC)");
+    GDL_REQUIRE(((uintptr_t)map & (layout == GDL_LAYOUT_NHWC ? 15 : 3)) == 0, "feature_diversity: map must be %d-byte aligned",
+                layout == GDL_LAYOUT_NHWC ? 16 : 4);
+    GDL_REQUIRE(ws_bytes >= feature_diversity_ws_bytes(n_img) && ((uintptr_t)ws & 255) == 0,
+                "feature_diversity: workspace of %zu bytes, 256-byte aligned", feature_diversity_ws_bytes(n_img));
+    return feature_diversity(map, dtype, layout, n_img, P, per_image, mean_out, accum, ws, (hipStream_t)stream);
+}
 size_t gdl_head_mtl_ce_workspace_bytes(int B) { return head_mtl_ce_ws_bytes(B); }
 int gdl_head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
                     int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out, float* out_a, float* out_v,

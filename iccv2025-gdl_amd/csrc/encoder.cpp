@@ -116,6 +116,7 @@ struct gdl_encoder {
     bool params_set = false;
     int64_t serial = 0;
     bool have_train_fwd = false;
+    bool have_fwd = false;  // any forward ran: the last block's output holds a map (gdl_encoder_feature_diversity)
     bool acc_last = false;  // the last forward ran its statistics through the integer accumulators (their flag words are valid)
     int64_t numel[GDL_ENC_NPARAMS];
     // gather tables: geometry -> workspace slot; built lazily on the first forward's stream
@@ -446,6 +447,7 @@ int gdl_encoder_bind(gdl_encoder_t* e, void* workspace, size_t bytes) {
     e->pack_dirty = true;
     e->tabs_dirty = true;
     e->have_train_fwd = false;
+    e->have_fwd = false;
     return GDL_OK;
 }
 
@@ -754,11 +756,30 @@ int gdl_encoder_forward(gdl_encoder_t* e, const float* x, int training, float* f
     const Block& last = e->blocks.back();
     if (feat_out) RC(avgpool_fwd(dt, last.z, feat_out, e->B, e->T, e->hf * e->wf, 512, st));
     if (fmap_nchw) RC(nhwc_to_nchw_f32(dt, last.z, fmap_nchw, e->n_img, e->hf, e->wf, 512, st));
+    e->have_fwd = true;
     if (training) {
         e->serial++;
         e->have_train_fwd = true;
     }
     return GDL_OK;
+}
+
+// The diversity monitor on the last forward's final map.  blocks.back().z is a buffer of its own (plan()): the forward's last
+// bn_act writes it, the backward only reads it (block_bwd_reduce, on the caller's stream), the side lane's weight gradients read
+// a1 / xin of the blocks and never this map.  So stream order behind the forward is all the launch needs.
+int gdl_encoder_feature_diversity(gdl_encoder_t* e, float* per_image, float* mean_out, float* accum, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    GDL_REQUIRE(e && mean_out && ws, "encoder_feature_diversity: null engine, mean_out or workspace");
+    if (!e->have_fwd) {
+        set_error("encoder_feature_diversity: no forward has run, there is no feature map");
+        return GDL_ERR_STATE;
+    }
+    const int P = e->hf * e->wf;
+    GDL_REQUIRE(P >= 1 && P <= 256, "encoder_feature_diversity: the final map has %d positions, at most 256 are supported", P);
+    GDL_REQUIRE(ws_bytes >= feature_diversity_ws_bytes(e->n_img) && ((uintptr_t)ws & 255) == 0,
+                "encoder_feature_diversity: workspace of %zu bytes, 256-byte aligned", feature_diversity_ws_bytes(e->n_img));
+    return feature_diversity(e->blocks.back().z, e->dtype, GDL_LAYOUT_NHWC, e->n_img, P, per_image, mean_out, accum, ws,
+                             (hipStream_t)stream);
 }
 
 // reductions + finalize of one BatchNorm's backward: gamma / beta gradients and coef.  `count`: elements per channel the

@@ -173,6 +173,10 @@ size_t head_mtl_ce_ws_bytes(int B);
 int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
                 int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out, float* out_a, float* out_v,
                 float* losses, float* g_f, float* g_a, float* g_v, float* dfa, float* dfv, int B, int n, void* ws, hipStream_t st);
+// diversity.hip: main.py's get_feature_diversity over a [n_img][P][512] (NHWC, f32 / bf16) or [n_img][512][P] (NCHW, f32) map
+size_t feature_diversity_ws_bytes(int n_img);
+int feature_diversity(const void* map, int dtype, int layout, int n_img, int P, float* per_image, float* mean_out, float* accum,
+                      void* ws, hipStream_t st);
 int head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out, float* y_out,
                     int B, int n, hipStream_t st);
 int head_concat_bwd(const float* x, const float* y, const float* W, const float* g_x_out, const float* g_y_out,

@@ -9,7 +9,12 @@ from ._lib import GdlError  # noqa: F401
 
 
 def __getattr__(name):
-    """`gdl.DGLTrainer` / `gdl.UnimodalTrainer`: the two runners, imported on first use (they import torch)."""
+    """`gdl.DGLTrainer` / `gdl.UnimodalTrainer`: the two runners, and `gdl.feature_diversity`, main.py's per-step monitor on a
+    feature map -- imported on first use (they import torch)."""
+    if name == "feature_diversity":
+        from .diversity import feature_diversity
+
+        return feature_diversity
     if name == "DGLTrainer":
         from .trainer import DGLTrainer
 

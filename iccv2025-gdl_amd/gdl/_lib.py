@@ -12,6 +12,7 @@ SO_PATH = os.environ.get("GDL_LIB") or os.path.join(os.path.dirname(_HERE), "csr
 GDL_F32, GDL_BF16 = 0, 1
 GDL_AUDIO, GDL_VISUAL = 0, 1
 GATHER_FWD, GATHER_DGRAD = 0, 1
+GDL_LAYOUT_NHWC, GDL_LAYOUT_NCHW = 0, 1
 ENC_NPARAMS, ENC_NBN = 60, 20
 
 _C = {"i": ctypes.c_int, "p": ctypes.c_void_p, "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double,
@@ -107,6 +108,9 @@ SIGNATURES = {
     "gdl_head_cls_ce": ("i", "pppp" + "f" + "pppp" + "iii" + "p"),
     "gdl_head_mtl_ce_workspace_bytes": ("z", "i"),
     "gdl_head_mtl_ce": ("i", "pppp" + "i" + "pp" + "i" + "p" + "fi" + "ppp" + "p" + "ppp" + "pp" + "ii" + "pz" + "p"),
+    "gdl_feature_diversity_workspace_bytes": ("z", "i"),
+    "gdl_feature_diversity": ("i", "p" + "iiiii" + "ppp" + "pz" + "p"),
+    "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),
     "gdl_head_concat_fwd": ("i", "ppppppp" + "ii" + "p"),
     "gdl_head_concat_bwd": ("i", "pppppp" + "ii" + "pppp" + "ii" + "p"),
     "gdl_softmax_ce": ("i", "ppf" + "pp" + "ii" + "p"),

@@ -109,6 +109,26 @@ class EncoderEngine:
         self._keep = x  # the kernels read x asynchronously
         return feat, fmap
 
+    def feature_diversity(self, per_image=False, out=None, accum=None):
+        """main.py's get_feature_diversity (:77-89) of the final map of the last forward (training or eval), read where the
+        engine keeps it (NHWC, the storage dtype; float32 arithmetic), enqueued on the CURRENT stream -- call it on the stream
+        that ran the forward, before the next forward (gdl_encoder_feature_diversity).  Returns a 0-dim device tensor, no host
+        sync; per_image=True: (mean, [n_img] per-image values).  out: a float32 device tensor whose first element receives the
+        mean instead of a new one; accum: 2 float32 device elements, [0] += mean, [1] += 1 (an epoch's sum and count).  The
+        engine owns the launch's workspace: calls on one engine must be ordered on one stream."""
+        if getattr(self, "_div_ws", None) is None:
+            from .diversity import workspace
+
+            with torch.cuda.device(self.device):
+                self._div_ws = workspace(self.out_shape[0], self.device)
+        with torch.cuda.device(self.device):
+            out = out if out is not None else torch.empty(1, device=self.device)
+            per = torch.empty(self.out_shape[0], device=self.device) if per_image else None
+        L.call("gdl_encoder_feature_diversity", self.h, L.ptr(per), out.data_ptr(), None if accum is None else accum.data_ptr(),
+               L.ptr(self._div_ws), self._div_ws.numel(), L.cur_stream())
+        m = out.reshape(-1)[0]
+        return (m, per) if per_image else m
+
     @property
     def serial(self):
         return self.lib.gdl_encoder_forward_serial(self.h)

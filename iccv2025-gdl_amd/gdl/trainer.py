@@ -185,6 +185,8 @@ class ArenaTrainer:
         # gradient modulation (a subclass calls `_setup_modulation`): None = the step launches none of its kernels
         self._mod = None
         self._mod_now = False
+        # the feature-diversity monitor (a subclass calls `_setup_diversity`): () = nothing allocated, nothing launched
+        self._div_keys = ()
 
     def _setup_modulation(self, marks, noise, alpha, seed):
         """OGM / OGM-GE over the gradient arena: marks[i] = 0 (untouched), 1 (audio) or 2 (visual) per arena tensor; `noise` =
@@ -203,6 +205,36 @@ class ArenaTrainer:
         """(like `_check_optimizer`: before the model is touched)"""
         if modulation not in MODULATIONS:
             raise ValueError(f"{cls.__name__}: modulation must be one of {MODULATIONS} (main.py --modulation), got {modulation!r}")
+
+    def _setup_diversity(self, keys):
+        """main.py's per-step feature-diversity monitor (:77-89, :183-184) for the encoders named by `keys` ("a_diversity" /
+        "v_diversity"): `div[i]` = the last step's value, `div_acc[i]` = (sum, count) since the last `epoch_diversity` reset --
+        both written by the kernel in stream order.  Not part of `state_dict()`: the script restarts them every epoch."""
+        self._div_keys = tuple(keys)
+        self.div = torch.zeros(len(keys), device=self.device)
+        self.div_acc = torch.zeros((len(keys), 2), device=self.device)
+
+    def _diversity(self, eng, i):
+        """gdl_encoder_feature_diversity behind `eng`'s training forward, on the current (= that forward's) stream"""
+        if self._div_keys:
+            eng.feature_diversity(out=self.div[i:i + 1], accum=self.div_acc[i])
+
+    def epoch_diversity(self, reset=True):
+        """{a_diversity, v_diversity} (the encoders this runner has): the means of the per-step values since the last reset, as
+        main.py:356 divides its running sums by the number of steps -- one host copy for the whole epoch.  NaN before any step.
+        reset: start a new epoch.  With a process group the values are the local rank's."""
+        if not self._div_keys:
+            raise L.GdlError(f"{type(self).__name__}.epoch_diversity: the monitor is off (diversity=False)")
+        acc = self.div_acc.cpu().numpy().astype("float64")
+        if reset:
+            self.div_acc.zero_()
+        return {k: (float(a[0] / a[1]) if a[1] > 0 else float("nan")) for k, a in zip(self._div_keys, acc)}
+
+    def _read_diversity(self, r):
+        """(read(), behind its synchronisation) the last step's values under their keys; nothing when the monitor is off"""
+        if self._div_keys:
+            r.update(zip(self._div_keys, (float(v) for v in self.div.cpu().numpy())))
+        return r
 
     def _opt_state(self):
         """{name: arena} of the chosen optimizer's state: momentum (sgd), exp_avg + exp_avg_sq (Adam), state_sum (AdaGrad)."""
@@ -314,7 +346,8 @@ class ArenaTrainer:
 class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
-                 modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True):
+                 modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True,
+                 diversity=False):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
@@ -326,7 +359,13 @@ class DGLTrainer(ArenaTrainer):
         detach_fused, drop_head_uni: the two gradient truncations DGL is made of (mode="dgl"; the defaults are DGL itself).
         drop_head_uni=False: the fusion head also learns from the unimodal losses -- the unmodified AVClassifier_DGL under ONE
         backward of loss_f + alpha (loss_a + loss_v).  detach_fused=False (concat and sum heads): loss_f also reaches the encoders.
-        Both False: the multi-task baseline of main.py:177, `alpha` being the scripts' --gamma."""
+        Both False: the multi-task baseline of main.py:177, `alpha` being the scripts' --gamma.
+        diversity: main.py's feature-diversity monitor ("Audio similar / Visual similar", :77-89, :183-184, :356) -- True: each
+        encoder's value is computed right behind its training forward on that encoder's own stream, in every form of the step;
+        `read()` gains `a_diversity` / `v_diversity`, `epoch_diversity()` returns the means since its last reset.  Off (the
+        default) nothing is allocated or launched.  With a process group the values are the LOCAL rank's (the script's
+        DataParallel averages over the gathered batch = the mean of the ranks' values at equal local batches).  The Swin visual
+        branch returns pooled tokens, no map: refused there.  Not part of `state_dict()`."""
         self._check_optimizer(optimizer)
         self._check_modulation(modulation)
         self.model = model
@@ -417,6 +456,9 @@ class DGLTrainer(ArenaTrainer):
             if not self.detach_fused and self.head not in ("concat", "sum"):
                 raise L.GdlError(f"DGLTrainer: detach_fused=False is built for the concat and sum heads, not for {self.head!r} (its "
                                  "fused path into the features needs kernels of its own)")
+        if diversity and self.vis_swin:
+            raise L.GdlError("DGLTrainer: diversity=True needs each encoder's final feature map [N, 512, h, w]; the Swin visual "
+                             "branch has none (its encoder returns pooled tokens)")
         self.modulation = modulation
         self.modulation_starts, self.modulation_ends = int(modulation_starts), int(modulation_ends)
         self.seed = int(seed)
@@ -462,6 +504,8 @@ class DGLTrainer(ArenaTrainer):
             # gated head's fc_x / fc_y) live outside the arena: they are never updated but still part of the state.
             self.reducer.sync_state([self.params] + list(self._opt_state().values()) + self._replica_buffers())
         self.losses = torch.zeros(3, device=self.device)  # loss_f, loss_a, loss_v
+        if diversity:
+            self._setup_diversity(("a_diversity", "v_diversity"))
         self.eng_a = self.eng_v = None
 
     def _replica_buffers(self):
@@ -628,11 +672,13 @@ class DGLTrainer(ArenaTrainer):
                 wa, wv, ldw, ba, bv = L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3])
             with torch.cuda.stream(self.s_v):
                 self.eng_v.forward(image, True, feat_out=self.fv)
+                self._diversity(self.eng_v, 1)
                 L.call("gdl_head_uni_dfeat_w", L.ptr(self.fv), wv, ldw, bv, L.ptr(label), self.alpha, L.ptr(self.dfv), B, n,
                        self.dv, self.s_v.cuda_stream)
                 ev_v = self.s_v.record_event()
             with torch.cuda.stream(self.s_a):
                 self.eng_a.forward(audio, True, feat_out=self.fa)
+                self._diversity(self.eng_a, 0)
                 L.call("gdl_head_uni_dfeat", L.ptr(self.fa), wa, ldw, ba, L.ptr(label), self.alpha, L.ptr(self.dfa), B, n,
                        self.s_a.cuda_stream)
             # (host order: both forwards are enqueued before either backward, so neither chain waits for the host)
@@ -653,8 +699,10 @@ class DGLTrainer(ArenaTrainer):
             return
         with torch.cuda.stream(self.s_v):
             self.eng_v.forward(image, True, feat_out=self.fv)
+            self._diversity(self.eng_v, 1)
         with torch.cuda.stream(self.s_a):
             self.eng_a.forward(audio, True, feat_out=self.fa)
+            self._diversity(self.eng_a, 0)
         main.wait_stream(self.s_a)
         main.wait_stream(self.s_v)
         self._mark(main, "fwd_done")
@@ -881,4 +929,4 @@ class DGLTrainer(ArenaTrainer):
         if self._mod is not None and self._mod_now:  # the last step was modulated (the statistics above are the unmodulated ones)
             m = self.mod_stats[:5].cpu().numpy()
             r["ogm"] = dict(score_a=float(m[0]), score_v=float(m[1]), ratio_v=float(m[2]), coeff_a=float(m[3]), coeff_v=float(m[4]))
-        return r
+        return self._read_diversity(r)

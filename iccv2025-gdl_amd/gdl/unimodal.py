@@ -26,7 +26,10 @@ class UnimodalTrainer(ArenaTrainer):
     _script = "main.py"
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=None, max_norm=40.0, dtype=None, optimizer="sgd",
-                 process_group=None):
+                 process_group=None, diversity=False):
+        """diversity: main.py's feature-diversity monitor (:77-89, :183-184, :356) of this model's one encoder -- True: computed
+        right behind the training forward on the chain; `read()` gains `a_diversity` (audio) or `v_diversity` (visual),
+        `epoch_diversity()` returns its mean since the last reset.  Off (the default) nothing is allocated or launched."""
         self._check_optimizer(optimizer)
         if process_group is not None:
             raise L.GdlError("UnimodalTrainer: data-parallel runs (process_group) are not built for the unimodal baselines")
@@ -59,6 +62,8 @@ class UnimodalTrainer(ArenaTrainer):
         self.losses = torch.zeros(1, device=self.device)
         self.chain, self.lane = (self.s_a, self.s_v) if modality == "audio" else (self.s_v, self.s_a)
         self.eng = None
+        if diversity:
+            self._setup_diversity(("a_diversity" if modality == "audio" else "v_diversity",))
 
     # ------------------------------------------------------------------ setup per batch shape
     def _input(self, spec, image):
@@ -106,6 +111,7 @@ class UnimodalTrainer(ArenaTrainer):
             B, n, st = self.B, self.n_classes, main.cuda_stream
             self._mark(main, "start")
             self.eng.forward(x, True, feat_out=self.f)
+            self._diversity(self.eng, 0)
             self._mark(main, "fwd_done")
             L.call("gdl_head_cls_ce", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.pviews[1]), L.ptr(label), 1.0,
                    L.ptr(self.out), L.ptr(self.losses), L.ptr(self.dlogits), L.ptr(self.df), B, n, 512, st)
@@ -152,4 +158,4 @@ class UnimodalTrainer(ArenaTrainer):
         r = self._read_stats((self.eng,))
         loss = float(self.losses.cpu().numpy()[0])
         r.update(loss_f=loss, loss_a=loss, loss_v=loss, out=self.out.cpu().numpy())
-        return r
+        return self._read_diversity(r)

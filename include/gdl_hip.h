@@ -605,6 +605,38 @@ GDL_API int64_t gdl_encoder_forward_serial(const gdl_encoder_t* e);
  * nn.BatchNorm2d of the reference shows as inf / NaN in its outputs (backbone.py:45-48,104,144); here ask this. */
 GDL_API int gdl_encoder_bn_overflow(gdl_encoder_t* e, void* stream);
 
+/* ------------------------------------------------------------------ feature-diversity monitor
+ * main.py's get_feature_diversity (:77-89), which its training loop applies to each encoder's final feature map at every step
+ * (:183-184), averages over the epoch (:339-340, :356) and prints as "Audio similar / Visual similar" (:657, :662).  Per image,
+ * with x_p the C = 512 channels at position p (P = h w positions):
+ *   c_p = x_p - mean_C(x_p),  s_p = sqrt(sum_C c_p^2 / (C - 1)),  R_pq = (c_p . c_q) / (s_p s_q),  d = ||R||_F / P^2
+ * per_image[i] = d of image i (n_img floats, may be NULL), mean_out[0] = their mean.  accum (2 floats, may be NULL):
+ * accum[0] += mean_out[0], accum[1] += 1 -- an epoch's sum and count, written by the launch itself in stream order, so a whole
+ * epoch needs no host sync.  All arithmetic is float32 whatever the storage type (a bf16 map is widened; the centred values are
+ * never rounded); the mean sums the n_img terms in one fixed order (no floating-point atomics): every output is bit-reproducible
+ * from run to run.  A position whose 512 channels are all equal has s_p = 0: NaN for that image and for the mean, as the
+ * script's 0 / 0 gives.
+ *   layout GDL_LAYOUT_NHWC: map [n_img][P][C] of `dtype` (float32 or bf16; the engine's activations), 16-byte aligned;
+ *   layout GDL_LAYOUT_NCHW: map [n_img][C][P] float32 (the tensor the drop-in modules return), 4-byte aligned.
+ * `ws` (gdl_feature_diversity_workspace_bytes(n_img), 256-byte aligned, so that the counter's line holds nothing else): a ticket
+ * counter on a 256-byte line of its own and n_img floats; the caller zeroes it ONCE, every launch that runs to its end leaves
+ * the counter zero again (the engine's call, gdl_encoder_feature_diversity, asks the same of its `ws`).  Launches sharing one
+ * `ws` must be ordered on one stream.  GDL_ERR_ARG, with a message and without a launch: C != 512, P outside [1, 256],
+ * n_img < 1, a null map / mean_out / ws, a short ws, bf16 with NCHW, a misaligned pointer. */
+#define GDL_LAYOUT_NHWC 0
+#define GDL_LAYOUT_NCHW 1
+GDL_API size_t gdl_feature_diversity_workspace_bytes(int n_img);
+GDL_API int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int P, int C, float* per_image,
+                                  float* mean_out, float* accum, void* ws, size_t ws_bytes, void* stream);
+/* The same on the final map of the engine's last forward, training or eval (the last block's output, n_img x h w x 512 in the
+ * engine's storage type; n_img, h, w: gdl_encoder_out_shape).  GDL_ERR_STATE before any forward.  Launch it on the stream that
+ * ran the forward: stream order is what protects the buffer.  Nothing but the next gdl_encoder_forward writes it -- the
+ * backward only reads it (the last block's ReLU mask and BatchNorm reductions), on the caller's stream, and the side lane's
+ * weight gradients read the blocks' inputs and never this map -- so the call may stand in front of the backward, behind it,
+ * or beside it on another stream that has waited for the forward, as long as it is ordered before the next forward. */
+GDL_API int gdl_encoder_feature_diversity(gdl_encoder_t* e, float* per_image, float* mean_out, float* accum, void* ws,
+                                          size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ measurement tap
  * Optional HIP-event timing of every kernel launch (off by default).  While enabled, each
  * launcher records an event pair on the launching stream and its algorithmic work (flops for
