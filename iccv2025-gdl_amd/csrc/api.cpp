@@ -308,6 +308,21 @@ int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int
                 "feature_diversity: workspace of %zu bytes, 256-byte aligned", feature_diversity_ws_bytes(n_img));
     return feature_diversity(map, dtype, layout, n_img, P, per_image, mean_out, accum, ws, (hipStream_t)stream);
 }
+size_t gdl_journal_bytes(int64_t capacity) { return journal_bytes(capacity); }
+int gdl_journal_append(void* journal, int64_t capacity, const float* losses, int n_losses, const float* stats, const float* out_a,
+                       const float* out_v, int64_t n_logits, const float* div_a, const float* div_v, const float* ogm,
+                       void* stream) {
+    GDL_REQUIRE(journal, "journal_append: null journal");
+    GDL_REQUIRE(capacity >= 1, "journal_append: capacity must be at least 1 row, got %lld", (long long)capacity);
+    GDL_REQUIRE(n_losses == 1 || n_losses == 3, "journal_append: n_losses must be 3, or 1 (the one loss in all three columns), got %d",
+                n_losses);
+    GDL_REQUIRE(losses && stats, "journal_append: null losses or stats");
+    GDL_REQUIRE(n_logits >= 0, "journal_append: n_logits must not be negative, got %lld", (long long)n_logits);
+    GDL_REQUIRE(n_logits > 0 || (!out_a && !out_v), "journal_append: out_a / out_v given with n_logits = 0 (the mean of no values)");
+    GDL_REQUIRE(((uintptr_t)journal & 15) == 0, "journal_append: the journal must be 16-byte aligned");
+    return journal_append(journal, capacity, losses, n_losses, stats, out_a, out_v, n_logits, div_a, div_v, ogm,
+                          (hipStream_t)stream);
+}
 size_t gdl_head_mtl_ce_workspace_bytes(int B) { return head_mtl_ce_ws_bytes(B); }
 int gdl_head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
                     int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out, float* out_a, float* out_v,

@@ -177,6 +177,11 @@ int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* 
 size_t feature_diversity_ws_bytes(int n_img);
 int feature_diversity(const void* map, int dtype, int layout, int n_img, int P, float* per_image, float* mean_out, float* accum,
                       void* ws, hipStream_t st);
+// journal.hip: one row of the scripts' per-step log, its epoch sums and the cursor, all in the caller's device buffer
+size_t journal_bytes(int64_t capacity);
+int journal_append(void* journal, int64_t capacity, const float* losses, int n_losses, const float* stats, const float* out_a,
+                   const float* out_v, int64_t n_logits, const float* div_a, const float* div_v, const float* ogm,
+                   hipStream_t st);
 int head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out, float* y_out,
                     int B, int n, hipStream_t st);
 int head_concat_bwd(const float* x, const float* y, const float* W, const float* g_x_out, const float* g_y_out,

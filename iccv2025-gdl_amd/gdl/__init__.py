@@ -10,7 +10,12 @@ from ._lib import GdlError  # noqa: F401
 
 def __getattr__(name):
     """`gdl.DGLTrainer` / `gdl.UnimodalTrainer`: the two runners, and `gdl.feature_diversity`, main.py's per-step monitor on a
-    feature map -- imported on first use (they import torch)."""
+    feature map, and `gdl.journal`, the step journal's module (`gdl.journal.COLUMNS`) -- imported on first use (they import
+    torch)."""
+    if name == "journal":
+        import importlib
+
+        return importlib.import_module(".journal", __name__)
     if name == "feature_diversity":
         from .diversity import feature_diversity
 

@@ -14,6 +14,7 @@ GDL_AUDIO, GDL_VISUAL = 0, 1
 GATHER_FWD, GATHER_DGRAD = 0, 1
 GDL_LAYOUT_NHWC, GDL_LAYOUT_NCHW = 0, 1
 ENC_NPARAMS, ENC_NBN = 60, 20
+GDL_JOURNAL_COLS = 16
 
 _C = {"i": ctypes.c_int, "p": ctypes.c_void_p, "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double,
       "l": ctypes.c_int64, "s": ctypes.c_char_p}
@@ -111,6 +112,8 @@ SIGNATURES = {
     "gdl_feature_diversity_workspace_bytes": ("z", "i"),
     "gdl_feature_diversity": ("i", "p" + "iiiii" + "ppp" + "pz" + "p"),
     "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),
+    "gdl_journal_bytes": ("z", "l"),
+    "gdl_journal_append": ("i", "pl" + "pi" + "p" + "ppl" + "pp" + "p" + "p"),
     "gdl_head_concat_fwd": ("i", "ppppppp" + "ii" + "p"),
     "gdl_head_concat_bwd": ("i", "pppppp" + "ii" + "pppp" + "ii" + "p"),
     "gdl_softmax_ce": ("i", "ppf" + "pp" + "ii" + "p"),

@@ -187,6 +187,8 @@ class ArenaTrainer:
         self._mod_now = False
         # the feature-diversity monitor (a subclass calls `_setup_diversity`): () = nothing allocated, nothing launched
         self._div_keys = ()
+        # the step journal (a subclass calls `_setup_journal`): None = nothing allocated, nothing launched
+        self._journal = None
 
     def _setup_modulation(self, marks, noise, alpha, seed):
         """OGM / OGM-GE over the gradient arena: marks[i] = 0 (untouched), 1 (audio) or 2 (visual) per arena tensor; `noise` =
@@ -235,6 +237,67 @@ class ArenaTrainer:
         if self._div_keys:
             r.update(zip(self._div_keys, (float(v) for v in self.div.cpu().numpy())))
         return r
+
+    @classmethod
+    def _check_journal(cls, journal):
+        """(like `_check_optimizer`: before the model is touched) the capacity in steps, 0 = off"""
+        if isinstance(journal, bool) or not isinstance(journal, int) or journal < 0:
+            raise ValueError(f"{cls.__name__}: journal must be a capacity in steps (an int >= 0, 0 = off), got {journal!r}")
+        return journal
+
+    def _setup_journal(self, capacity, logits):
+        """The scripts' per-step log on the device (gdl.journal, csrc/journal.hip): a ring of `capacity` rows, the epoch's sums
+        and the cursor in one device buffer; `_finish_step` appends a row per step.  0 = off.  logits: whether this runner has
+        unimodal logits (`_journal_logits`) for the abs_out_a / abs_out_v columns.  Not part of `state_dict()`: the script
+        restarts its sums every epoch."""
+        self._journal_has_logits = bool(logits)
+        if capacity:
+            from .journal import Journal
+
+            self._journal = Journal(capacity, self.device)
+
+    def _journal_logits(self):
+        """(a subclass with unimodal logits overrides it) the tensors behind the abs_out_a / abs_out_v columns, or None"""
+        return None, None
+
+    def _journal_append(self, st):
+        """One row behind the update on the step's main stream `st`: every source is final there -- the losses, the logits and
+        `mod_stats` were written on it, the statistics just before, and `_finish_step` has joined both chains (the diversity
+        values).  The call has the same arguments at every step but for the OGM pointer, which follows `_mod_now`."""
+        out_a, out_v = self._journal_logits()
+        n_logits = 0 if out_a is None and out_v is None else (out_a if out_a is not None else out_v).numel()
+        div = {k: self.div.data_ptr() + 4 * i for i, k in enumerate(self._div_keys)}
+        ogm = L.ptr(self.mod_stats) if self._mod is not None and self._mod_now else None
+        self._journal.append(self.losses, L.ptr(self.stats), L.ptr(out_a), L.ptr(out_v), n_logits, div.get("a_diversity"),
+                             div.get("v_diversity"), ogm, st)
+
+    def journal(self, reset=True):
+        """The step journal since the last reset -- one synchronisation and ONE host copy for what the scripts fetch value by
+        value at every step.  Returns a dict:
+          columns     gdl.journal.COLUMNS, the 16 names
+          rows        float32 [n, 16], the retained rows (the newest `journal` of them) in step order; a column with no source
+                      in this configuration -- or, for the OGM columns, at a step that was not modulated -- holds NaN
+          first_step  the 0-based count of steps this trainer had taken before the step of rows[0] (`self.steps` then)
+          count       rows appended since the last reset
+          dropped     max(0, count - capacity): rows the ring has overwritten
+          means       {name: sum / count} in float64 for the columns among loss_f .. v_diversity that this trainer feeds, from
+                      float64 sums the device adds to in step order (the script's `_loss += x.item()`, then `/ len(dataloader)`):
+                      over ALL `count` steps, whether or not the ring overflowed; NaN when count is 0
+        reset: start a new epoch -- the cursor and the sums are zeroed, ordered on the stream.  main_dgl.py's CSV rows are
+        rows[:, 5:7], its epoch line means["loss_f"], means["loss_a"], means["loss_v"].  With a process group the losses and
+        logits are the local rank's, the gradient statistics those of the reduced gradient."""
+        if self._journal is None:
+            raise L.GdlError(f"{type(self).__name__}.journal: the journal is off (journal=0)")
+        from .journal import COLUMNS, N_ACC
+
+        torch.cuda.synchronize(self.device)
+        count, acc, rows = self._journal.fetch()
+        if reset:
+            self._journal.reset()
+        fed = set(COLUMNS[:7]) | set(self._div_keys) | ({"abs_out_a", "abs_out_v"} if self._journal_has_logits else set())
+        means = {k: (float(acc[i] / count) if count > 0 else float("nan")) for i, k in enumerate(COLUMNS[:N_ACC]) if k in fed}
+        return {"columns": COLUMNS, "rows": rows, "first_step": self.steps - rows.shape[0], "count": count,
+                "dropped": max(0, count - self._journal.capacity), "means": means}
 
     def _opt_state(self):
         """{name: arena} of the chosen optimizer's state: momentum (sgd), exp_avg + exp_avg_sq (Adam), state_sum (AdaGrad)."""
@@ -311,6 +374,8 @@ class ArenaTrainer:
         else:
             L.call("gdl_optim_adagrad_step", self.opt, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.state_sum),
                    stats, gs, self.lr, ADAGRAD_EPS, self.wd, self.steps + 1, st)
+        if self._journal is not None:
+            self._journal_append(st)
         self._mark(main, "end")
         if self.stats_log is not None and self.stats_log_pos is not None and self.stats_log_pos < self.stats_log.shape[0]:
             self.stats_log[self.stats_log_pos].copy_(self.stats[:2], non_blocking=True)
@@ -347,7 +412,7 @@ class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
                  modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True,
-                 diversity=False):
+                 diversity=False, journal=0):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
@@ -365,9 +430,19 @@ class DGLTrainer(ArenaTrainer):
         `read()` gains `a_diversity` / `v_diversity`, `epoch_diversity()` returns the means since its last reset.  Off (the
         default) nothing is allocated or launched.  With a process group the values are the LOCAL rank's (the script's
         DataParallel averages over the gathered batch = the mean of the ranks' values at equal local batches).  The Swin visual
-        branch returns pooled tokens, no map: refused there.  Not part of `state_dict()`."""
+        branch returns pooled tokens, no map: refused there.  Not part of `state_dict()`.
+        journal: the scripts' per-step log kept on the device -- the capacity in steps of a ring of rows (gdl.journal.COLUMNS:
+        the three losses, total_norm / clip_coef / audio_grad_sum / visual_grad_sum, mean |out_a| / mean |out_v|, the two
+        diversity values, OGM's scores / ratio / coefficients), written by one launch behind the update at every step together
+        with the epoch's float64 sums; `tr.journal()` is then ONE host copy per epoch where the script synchronises at every
+        step (main_dgl.py:132-165).  mode="dgl" feeds the abs_out columns, the joint step has no unimodal logits (NaN; loss_a /
+        loss_v are whatever `read()` reports); the diversity columns need diversity=True, the OGM columns a modulated step.
+        Every form of the step, the Swin composition and a process group are allowed: with a group the losses and logits are
+        the LOCAL rank's and the gradient statistics those of the reduced gradient.  0 (the default): nothing is allocated or
+        launched and the step is bit for bit what it was.  Not part of `state_dict()`."""
         self._check_optimizer(optimizer)
         self._check_modulation(modulation)
+        self._check_journal(journal)
         self.model = model
         self.mode = mode
         self.alpha = float(alpha)
@@ -506,7 +581,11 @@ class DGLTrainer(ArenaTrainer):
         self.losses = torch.zeros(3, device=self.device)  # loss_f, loss_a, loss_v
         if diversity:
             self._setup_diversity(("a_diversity", "v_diversity"))
+        self._setup_journal(journal, self.mode == "dgl")
         self.eng_a = self.eng_v = None
+
+    def _journal_logits(self):
+        return (self.out_a, self.out_v) if self.mode == "dgl" else (None, None)
 
     def _replica_buffers(self):
         """Every tensor of the replica that is not in the flat arenas: BatchNorm running statistics and counters of

@@ -26,11 +26,16 @@ class UnimodalTrainer(ArenaTrainer):
     _script = "main.py"
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=None, max_norm=40.0, dtype=None, optimizer="sgd",
-                 process_group=None, diversity=False):
+                 process_group=None, diversity=False, journal=0):
         """diversity: main.py's feature-diversity monitor (:77-89, :183-184, :356) of this model's one encoder -- True: computed
         right behind the training forward on the chain; `read()` gains `a_diversity` (audio) or `v_diversity` (visual),
-        `epoch_diversity()` returns its mean since the last reset.  Off (the default) nothing is allocated or launched."""
+        `epoch_diversity()` returns its mean since the last reset.  Off (the default) nothing is allocated or launched.
+        journal: the script's per-step log kept on the device, as DGLTrainer's -- the capacity in steps of the ring `tr.journal()`
+        hands back with the epoch's means in one host copy.  The script's unimodal model returns `out, out, out`: the one loss
+        fills loss_f / loss_a / loss_v and mean |out| both abs_out columns; the absent modality's grad_sum reads 0.0, its
+        diversity column NaN.  0 (the default): nothing is allocated or launched."""
         self._check_optimizer(optimizer)
+        self._check_journal(journal)
         if process_group is not None:
             raise L.GdlError("UnimodalTrainer: data-parallel runs (process_group) are not built for the unimodal baselines")
         modality = getattr(model, "modality", None)
@@ -64,6 +69,10 @@ class UnimodalTrainer(ArenaTrainer):
         self.eng = None
         if diversity:
             self._setup_diversity(("a_diversity" if modality == "audio" else "v_diversity",))
+        self._setup_journal(journal, True)
+
+    def _journal_logits(self):
+        return self.out, self.out
 
     # ------------------------------------------------------------------ setup per batch shape
     def _input(self, spec, image):

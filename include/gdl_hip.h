@@ -637,6 +637,44 @@ GDL_API int gdl_feature_diversity(const void* map, int dtype, int layout, int n_
 GDL_API int gdl_encoder_feature_diversity(gdl_encoder_t* e, float* per_image, float* mean_out, float* accum, void* ws,
                                           size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ step journal
+ * The scripts' per-step log kept on the device.  main_dgl.py appends [audio_grad_sum, visual_grad_sum] to a CSV at every step
+ * (:132-152), adds loss_f / loss_a / loss_v `.item()` into Python floats whose sums over len(dataloader) are its epoch line
+ * (:156-165), and prints the losses with torch.abs(out_a).mean() / torch.abs(out_v).mean() every 100 steps (:125-127, :144-146);
+ * main.py adds the two diversity sums (:339-340) and OGM's `ratio v / coefficient v / coefficient a` (:308-312).  Each of these
+ * is a host sync per step there.  gdl_journal_append writes them as ONE row of GDL_JOURNAL_COLS floats per step into a ring in
+ * the caller's device buffer and adds the row to the epoch's sums beside it: a whole epoch needs no host sync and one host copy.
+ * Columns of a row:
+ *    0-2   loss_f, loss_a, loss_v            `losses` (n_losses = 3), or losses[0] in all three (n_losses = 1: the unimodal
+ *                                            model returns `out, out, out`)
+ *    3-6   total_norm, clip_coef, audio_grad_sum, visual_grad_sum      gdl_optim_grad_stats' stats[0..3]
+ *    7-8   mean |out_a|, mean |out_v|        over n_logits = B n values each (main_dgl.py:146); either pointer may be NULL
+ *    9-10  a_diversity, v_diversity          one float each (gdl_feature_diversity's mean_out), may be NULL
+ *   11-15  score_a, score_v, ratio_v, coeff_a, coeff_v                 gdl_optim_modulate's mod_stats[0..4], may be NULL
+ * Columns 0-6 and 9-15 are copies of the source floats, bit for bit; a NULL source writes NaN into its columns.  Columns 7-8:
+ * float32, one fixed order -- thread t of the one 256-thread block adds |x[t]|, |x[t + 256]|, ... in turn, a butterfly folds
+ * each wave, the four wave sums are added as (w0 + w1) + (w2 + w3), one division by (float)n_logits; no floating-point atomic,
+ * so two launches on the same data give the same bits, and (all terms being non-negative) the relative error against the
+ * exact mean of the same values is at most (ceil(n_logits / 256) + 8 + 1) 2^-24 for n_logits < 2^24.
+ * The buffer (gdl_journal_bytes(capacity) bytes, 16-byte aligned), header, then accumulators, then rows:
+ *   byte   0  int64  count: rows appended since the header was last zeroed;  byte 8: three reserved int64
+ *   byte  32  double acc[12]: acc[c] += (double)row[c] for c = 0..10 at every append, in step order -- the script's
+ *             `_loss += x.item()` exactly, so acc[c] / count is its epoch mean over ALL `count` steps whether or not the ring has
+ *             wrapped; a NaN propagates as it does there; acc[11] is unused
+ *   byte 128  float  rows[capacity][GDL_JOURNAL_COLS]: the append writes row count % capacity, then count becomes count + 1 --
+ *             the ring keeps the newest `capacity` rows
+ * Zero the first 128 bytes (hipMemsetAsync, ordered on the stream) before the first append and to start a new epoch; the rows
+ * need no clearing.  No host-side state enters the launch -- the cursor lives in the buffer -- so every step's call has the
+ * same arguments and may be captured into a graph.  One launch of one work-group; appends to one buffer must be ordered on one
+ * stream, behind whatever writes the sources.  GDL_ERR_ARG, with a message and without a launch: journal NULL or not 16-byte
+ * aligned, capacity < 1, n_losses not 1 or 3, losses or stats NULL, n_logits < 0, a non-NULL out_a / out_v with n_logits = 0.
+ * gdl_journal_bytes: 128 + 64 capacity; 0 for capacity < 1. */
+#define GDL_JOURNAL_COLS 16
+GDL_API size_t gdl_journal_bytes(int64_t capacity);
+GDL_API int gdl_journal_append(void* journal, int64_t capacity, const float* losses, int n_losses, const float* stats,
+                               const float* out_a, const float* out_v, int64_t n_logits, const float* div_a, const float* div_v,
+                               const float* ogm, void* stream);
+
 /* ------------------------------------------------------------------ measurement tap
  * Optional HIP-event timing of every kernel launch (off by default).  While enabled, each
  * launcher records an event pair on the launching stream and its algorithmic work (flops for
