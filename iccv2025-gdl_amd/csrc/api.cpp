@@ -449,6 +449,20 @@ int gdl_logspec(const float* wave, int B, int n_samples, int n_fft, int hop, int
     GDL_REQUIRE(pad_mode == GDL_PAD_CONSTANT || n_samples > n_fft / 2, "logspec: reflect padding needs more than n_fft/2 samples");
     return logspec(wave, B, n_samples, n_fft, hop, pad_mode == GDL_PAD_REFLECT, out, (hipStream_t)stream);
 }
+int gdl_wave_logspec(const void* src, size_t src_bytes, const int64_t* desc, int B, int n_samples, int n_fft, int hop, int pad_mode,
+                     int out_h, int out_w, float* wave_out, float* out, void* stream) {
+    GDL_REQUIRE(src && desc && out && src_bytes > 0 && B > 0 && n_samples > 0 && hop > 0, "wave_logspec: bad arguments");
+    GDL_REQUIRE(((uintptr_t)src & 3) == 0 && ((uintptr_t)desc & 7) == 0, "wave_logspec: src must be 4-byte, desc 8-byte aligned");
+    GDL_REQUIRE(B <= 65535 && n_samples < INT32_MAX - 4096, "wave_logspec: at most 65535 samples of less than 2^31 - 4096 values a launch");
+    GDL_REQUIRE(n_fft >= 16 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, "wave_logspec: n_fft must be a power of two in [16, 2048]");
+    GDL_REQUIRE(pad_mode == GDL_PAD_CONSTANT || pad_mode == GDL_PAD_REFLECT, "wave_logspec: pad_mode must be GDL_PAD_CONSTANT or GDL_PAD_REFLECT");
+    GDL_REQUIRE(pad_mode == GDL_PAD_CONSTANT || n_samples > n_fft / 2, "wave_logspec: reflect padding needs more than n_fft/2 samples");
+    GDL_REQUIRE(out_h >= 0 && out_w >= 0 && (out_h == 0) == (out_w == 0),
+                "wave_logspec: output size %d x %d must be 0 x 0 (the spectrogram as it is) or positive", out_h, out_w);
+    GDL_REQUIRE((int64_t)out_h * out_w < (int64_t)1 << 31, "wave_logspec: output size %d x %d is too large", out_h, out_w);
+    return wave_logspec(src, src_bytes, (const long long*)desc, B, n_samples, n_fft, hop, pad_mode == GDL_PAD_REFLECT, out_h, out_w,
+                        wave_out, out, (hipStream_t)stream);
+}
 int gdl_frames_normalize(const uint8_t* frames, int64_t n_img, int H, int W, const float* mean, const float* std, float* out,
                          void* stream) {
     GDL_REQUIRE(frames && out && mean && std && n_img > 0 && H > 0 && W > 0, "frames_normalize: bad arguments");

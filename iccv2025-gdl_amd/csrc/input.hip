@@ -1,4 +1,4 @@
-// input.hip -- the two device-side stages of the reference's input pipeline.
+// input.hip -- the device-side stages of the reference's input pipeline.
 //
 // 1. log-magnitude STFT of a clipped waveform, what every dataset of the reference computes per sample on the host:
 //        resamples[resamples > 1.] = 1.; resamples[resamples < -1.] = -1.
@@ -15,6 +15,10 @@
 //    (double-precision-generated) twiddle table in LDS.  12 032 frames x 257 bins x 512 samples is 3.2 GMAC for a
 //    B=64 CREMA-D batch -- microseconds of VALU time, so an FFT would buy nothing and the direct sum is the more
 //    accurate of the two in fp32.
+//    gdl_wave_logspec is the same transform with the datasets' waveform staging in front of it, in the same launch: the PCM
+//    decode scale, the mono mix-down, the tiling and the (random) window of librosa.load + np.tile + slicing
+//    (KSDataset.py:139-144 and the same lines of the other datasets), and np.resize behind it where a dataset has one.  The
+//    two kernels share ls_block(); they differ in where a sample of the window comes from and in the store.
 //
 // 2. ToTensor() + Normalize(mean, std) of decoded frames (CramedDataset.py:77-81): uint8 HWC -> float32 CHW,
 //    ((x / 255) - mean[c]) / std[c] in that order of fp32 operations (bit-identical to torchvision on the CPU).
@@ -27,7 +31,9 @@
 //    (what transforms.Resize calls on a PIL image), restated in tests/resize_ref.py: horizontal pass, then vertical, the
 //    intermediate rounded to uint8, 22-bit integer coefficients made from double-precision triangle weights.  All of it on
 //    pixels is int32, so the result equals the restatement bit for bit (tests/test_augment_gpu.py).
-//    What stays on the host: decoding the files, and drawing the boxes and flips (a few integers per frame, gdl/data.py).
+//    What stays on the host: decoding the files to PCM / uint8 frames, resampling the audio of the 22050 Hz datasets (CREMA-D,
+//    AVE: librosa's resampler is a third-party filter design that is not restated here), and drawing the window starts, boxes and
+//    flips (a few integers per sample, gdl/data.py).
 #include "common.h"
 #include "ops.h"
 
@@ -35,19 +41,55 @@ namespace gdl {
 
 constexpr int LS_FPB = 4;  // frames per block
 
-__global__ void logspec_kernel(const float* __restrict__ wave, float* __restrict__ out, int L, int n_fft, int hop, int frames,
-                               int reflect) {
+// Where the samples of a clip's fixed-length window come from.  at(p), 0 <= p < L, is the clipped sample p of the window.
+// gdl_logspec: the host has staged the batch, [B][L] float32.
+struct LsContiguous {
+    const float* w;
+    __device__ __forceinline__ float at(int p) const { return fminf(fmaxf(w[p], -1.f), 1.f); }
+};
+// gdl_wave_logspec: the decoded clip as the file stores it; sample p of the window is sample (start + p) mod len of the clip's
+// periodic extension (s0 = start mod len), decoded (int16: x / 32768, exact in fp32) and mixed down ((l + r) / 2, which is
+// np.mean over two channels in fp32).
+struct LsClip {
+    const unsigned char* clip;  // 4-byte aligned
+    unsigned len, s0;           // len < 2^31, s0 < len
+    int stereo, s16;
+    __device__ __forceinline__ float at(int p) const {
+        unsigned q = s0 + (unsigned)p;  // < 2^32
+        if (q >= len) {
+            q -= len;
+            if (q >= len) q %= len;  // only a clip shorter than the window wraps more than once
+        }
+        float v;
+        if (s16) {
+            if (stereo) {
+                const unsigned lr = ((const unsigned*)clip)[q];
+                v = ((float)(short)(lr & 0xffffu) * (1.f / 32768.f) + (float)(short)(lr >> 16) * (1.f / 32768.f)) / 2.f;
+            } else {
+                v = (float)((const short*)clip)[q] * (1.f / 32768.f);
+            }
+        } else {
+            const float* c = (const float*)clip;
+            v = stereo ? (c[2 * (size_t)q] + c[2 * (size_t)q + 1]) / 2.f : c[q];
+        }
+        return fminf(fmaxf(v, -1.f), 1.f);
+    }
+};
+
+// The transform of one block -- LS_FPB frames from f0 on, one thread per bin -- whatever the samples' source: twiddle table,
+// windowed frames into LDS, direct DFT, log magnitude.  False for a thread without a bin; lm[j] is the value of frame f0 + j.
+template <class Src>
+__device__ __forceinline__ bool ls_block(const Src& src, int L, int n_fft, int hop, int frames, int reflect, int f0, float (&lm)[LS_FPB]) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ls_smem[];
     float2* tw = (float2*)ls_smem;               // [n_fft] (cos, sin)(2 pi n / n_fft)
     float* xw = (float*)(tw + n_fft);            // [LS_FPB][n_fft] windowed frames
-    const int b = blockIdx.y, f0 = blockIdx.x * LS_FPB, bins = n_fft / 2 + 1, pad = n_fft / 2;
+    const int bins = n_fft / 2 + 1, pad = n_fft / 2;
     for (int n = threadIdx.x; n < n_fft; n += blockDim.x) {
         double s, c;
         sincospi(2.0 * (double)n / (double)n_fft, &s, &c);
         tw[n] = make_float2((float)c, (float)s);
     }
     __syncthreads();
-    const float* w = wave + (size_t)b * L;
     for (int i = threadIdx.x; i < LS_FPB * n_fft; i += blockDim.x) {
         const int j = i / n_fft, n = i - j * n_fft;
         int p = (f0 + j) * hop + n - pad;  // index into the unpadded signal
@@ -57,14 +99,14 @@ __global__ void logspec_kernel(const float* __restrict__ wave, float* __restrict
                 if (p < 0) p = -p;
                 if (p >= L) p = 2 * (L - 1) - p;
             }
-            if (p >= 0 && p < L) v = fminf(fmaxf(w[p], -1.f), 1.f);
+            if (p >= 0 && p < L) v = src.at(p);
         }
         const float hann = 0.5f - 0.5f * tw[n].x;  // periodic Hann
         xw[i] = v * hann;
     }
     __syncthreads();
     const int k = threadIdx.x;
-    if (k >= bins) return;
+    if (k >= bins) return false;
     float re[LS_FPB], im[LS_FPB];
 #pragma unroll
     for (int j = 0; j < LS_FPB; ++j) re[j] = 0.f, im[j] = 0.f;
@@ -81,10 +123,20 @@ __global__ void logspec_kernel(const float* __restrict__ wave, float* __restrict
         }
         idx = (idx + k) & msk;
     }
-    float* o = out + ((size_t)b * bins + k) * frames + f0;
+#pragma unroll
+    for (int j = 0; j < LS_FPB; ++j) lm[j] = logf(sqrtf(re[j] * re[j] + im[j] * im[j]) + 1e-7f);
+    return true;
+}
+
+__global__ void logspec_kernel(const float* __restrict__ wave, float* __restrict__ out, int L, int n_fft, int hop, int frames,
+                               int reflect) {
+    const int b = blockIdx.y, f0 = blockIdx.x * LS_FPB, bins = n_fft / 2 + 1;
+    float lm[LS_FPB];
+    if (!ls_block(LsContiguous{wave + (size_t)b * L}, L, n_fft, hop, frames, reflect, f0, lm)) return;
+    float* o = out + ((size_t)b * bins + threadIdx.x) * frames + f0;
 #pragma unroll
     for (int j = 0; j < LS_FPB; ++j)
-        if (f0 + j < frames) o[j] = logf(sqrtf(re[j] * re[j] + im[j] * im[j]) + 1e-7f);
+        if (f0 + j < frames) o[j] = lm[j];
 }
 
 int logspec_frames(int L, int hop) { return 1 + L / hop; }
@@ -96,6 +148,61 @@ int logspec(const float* wave, int B, int L, int n_fft, int hop, int reflect, fl
     hipLaunchKernelGGL(logspec_kernel, dim3(ceil_div(frames, LS_FPB), B), dim3(threads), lds, st, wave, out, L, n_fft, hop, frames,
                        reflect);
     GDL_CHECK_LAUNCH("logspec_kernel");
+    return GDL_OK;
+}
+
+// ---------------------------------------------------------------- waveform staging + log-magnitude STFT
+// logspec_kernel's grid and LDS; only the frame loader differs (LsClip), and the store: element e = k * frames + t of the
+// [bins][frames] spectrogram goes to every e + j * bins * frames < total of the sample's output, which is np.resize's flat
+// re-layout (total = out_h * out_w; an element past it is dropped) and the plain store for total = bins * frames.  A block
+// also writes its share of the staged window to wave_out when the caller wants it: samples [x * chunk, (x + 1) * chunk) for
+// block x of the clip, so that every sample is written once whatever hop and n_fft are.
+// A descriptor from a C caller may be anything: a sample whose clip does not lie inside the packed buffer, or whose window does
+// not lie inside its tiled length, is written as NaN and nothing of it is read.
+__global__ void wave_logspec_kernel(const unsigned char* __restrict__ src, long long src_bytes, const long long* __restrict__ desc,
+                                    float* __restrict__ wave_out, float* __restrict__ out, int L, int n_fft, int hop, int frames,
+                                    int reflect, long long total) {
+    const int b = blockIdx.y, f0 = blockIdx.x * LS_FPB, bins = n_fft / 2 + 1;
+    const long long* d = desc + (size_t)b * 6;
+    const long long off = d[0], len = d[1], ch = d[2], fmt = d[3], start = d[4], limit = d[5];
+    bool ok = off >= 0 && (off & 3) == 0 && off <= src_bytes && len >= 1 && len < (1ll << 31) && (ch == 1 || ch == 2) &&
+              (fmt == GDL_WAVE_F32 || fmt == GDL_WAVE_S16) && start >= 0 && limit < (1ll << 31) && start <= limit - L;
+    ok = ok && len * ch * (fmt == GDL_WAVE_S16 ? 2 : 4) <= src_bytes - off;  // (len * ch * 4 < 2^34)
+    const long long plane = (long long)bins * frames;
+    float* o = out + (size_t)b * (size_t)total;
+    const int chunk = (int)(((long long)L + gridDim.x - 1) / gridDim.x);
+    const long long w0l = (long long)blockIdx.x * chunk;
+    const int w0 = w0l < L ? (int)w0l : L, w1 = L - w0 < chunk ? L : w0 + chunk;
+    float* wo = wave_out ? wave_out + (size_t)b * L : nullptr;
+    if (!ok) {
+        if (threadIdx.x < bins)
+            for (int j = 0; j < LS_FPB; ++j)
+                if (f0 + j < frames)
+                    for (long long i = (long long)threadIdx.x * frames + f0 + j; i < total; i += plane) o[i] = __builtin_nanf("");
+        if (wo)
+            for (int p = w0 + threadIdx.x; p < w1; p += blockDim.x) wo[p] = __builtin_nanf("");
+        return;
+    }
+    const LsClip clip{src + off, (unsigned)len, (unsigned)(start % len), ch == 2, fmt == GDL_WAVE_S16};
+    if (wo)
+        for (int p = w0 + threadIdx.x; p < w1; p += blockDim.x) wo[p] = clip.at(p);
+    float lm[LS_FPB];
+    if (!ls_block(clip, L, n_fft, hop, frames, reflect, f0, lm)) return;
+#pragma unroll
+    for (int j = 0; j < LS_FPB; ++j)
+        if (f0 + j < frames)
+            for (long long i = (long long)threadIdx.x * frames + f0 + j; i < total; i += plane) o[i] = lm[j];
+}
+
+int wave_logspec(const void* src, size_t src_bytes, const long long* desc, int B, int L, int n_fft, int hop, int reflect, int out_h,
+                 int out_w, float* wave_out, float* out, hipStream_t st) {
+    const int frames = logspec_frames(L, hop), bins = n_fft / 2 + 1;
+    const int threads = (bins + 63) / 64 * 64;
+    const size_t lds = (size_t)n_fft * sizeof(float2) + (size_t)LS_FPB * n_fft * sizeof(float);
+    const long long total = out_h ? (long long)out_h * out_w : (long long)bins * frames;
+    hipLaunchKernelGGL(wave_logspec_kernel, dim3(ceil_div(frames, LS_FPB), B), dim3(threads), lds, st, (const unsigned char*)src,
+                       (long long)src_bytes, desc, wave_out, out, L, n_fft, hop, frames, reflect, total);
+    GDL_CHECK_LAUNCH("wave_logspec_kernel");
     return GDL_OK;
 }
 

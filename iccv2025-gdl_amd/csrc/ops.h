@@ -221,6 +221,8 @@ int head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const 
 // input.hip
 int logspec_frames(int L, int hop);
 int logspec(const float* wave, int B, int L, int n_fft, int hop, int reflect, float* out, hipStream_t st);
+int wave_logspec(const void* src, size_t src_bytes, const long long* desc, int B, int L, int n_fft, int hop, int reflect, int out_h,
+                 int out_w, float* wave_out, float* out, hipStream_t st);
 int frames_normalize(const unsigned char* in, size_t n_img, int H, int W, const float* mean, const float* std, float* out,
                      hipStream_t st);
 int resized_crop_box_ok(int box_h, int box_w, int out_h, int out_w);

@@ -131,6 +131,7 @@ SIGNATURES = {
     "gdl_head_film_joint_bwd": ("i", "p" * 12 + "ii" + "pz" + "p"),
     "gdl_logspec_frames": ("i", "ii"),
     "gdl_logspec": ("i", "p" + "iiiii" + "pp"),
+    "gdl_wave_logspec": ("i", "pzp" + "iiiiiii" + "ppp"),
     "gdl_frames_normalize": ("i", "p" + "lii" + "ppp" + "p"),
     "gdl_frames_resized_crop_box_ok": ("i", "iiii"),
     "gdl_frames_resized_crop": ("i", "pzp" + "iiiii" + "ppp" + "p"),

@@ -1,12 +1,14 @@
-"""Device-side stages of the reference's input pipeline over gdl_logspec / gdl_frames_normalize /
-gdl_frames_resized_crop.
+"""Device-side stages of the reference's input pipeline over gdl_logspec / gdl_wave_logspec /
+gdl_frames_normalize / gdl_frames_resized_crop.
 
 The reference computes all of them per sample on DataLoader workers (dataset/CramedDataset.py:58-95, KSDataset.py:136-190,
-VGGSoundDataset.py:110-160): a log-magnitude librosa STFT of the clipped waveform, and RandomResizedCrop(224) +
-RandomHorizontalFlip + ToTensor + Normalize (training) or Resize((224, 224)) + ToTensor + Normalize (evaluation) of the decoded
-frames.  Here a whole batch is one kernel launch each.  What stays on the host: file decoding, resampling and tiling / cropping
-of the waveform, decoding the frames to uint8, and drawing the crop boxes and flips -- a few integers per frame
-(random_augment_params); everything that touches a pixel runs on the device.
+VGGSoundDataset.py:110-160): librosa.load's PCM scale and mono mix-down, the tiling and the (random) window of the waveform, a
+log-magnitude librosa STFT of the clipped window, and RandomResizedCrop(224) + RandomHorizontalFlip + ToTensor + Normalize
+(training) or Resize((224, 224)) + ToTensor + Normalize (evaluation) of the decoded frames.  Here a whole batch is one kernel
+launch each (wave_log_spectrogram / stage_audio, resized_crop_frames / augment_frames).  What stays on the host: decoding the
+files to PCM samples and uint8 frames, resampling the audio of the 22050 Hz datasets (CREMA-D, AVE; the 16 kHz datasets' files
+are stored at their rate), and drawing the window starts, the crop boxes and the flips -- a few integers per sample
+(random_wave_starts, random_augment_params); everything that touches a sample's or a pixel's value runs on the device.
 
 Nothing is computed on the CPU: the functions that produce tensors need device tensors and the built library.
 """
@@ -48,6 +50,197 @@ def log_spectrogram(wave, n_fft=512, hop_length=353, pad_mode="constant", out=No
         raise ValueError("gdl: out must be a contiguous float32 tensor [B, n_fft//2+1, frames]")
     L.call("gdl_logspec", L.ptr(w), B, n, n_fft, hop_length, PAD_MODES[pad_mode], L.ptr(out), L.cur_stream())
     return out[0] if squeeze else out
+
+
+# ------------------------------------------------------------------ waveform staging (gdl_wave_logspec)
+GDL_WAVE_F32, GDL_WAVE_S16 = 0, 1  # include/gdl_hip.h
+_WAVE_FORMATS = {torch.float32: GDL_WAVE_F32, torch.int16: GDL_WAVE_S16}
+_WAVE_BYTES = {GDL_WAVE_F32: 4, GDL_WAVE_S16: 2}
+
+# The audio half of the reference datasets' __getitem__ as data.  rate: what librosa.load is asked for; tiling: ("times", 3) is
+# np.tile(samples, 3), ("double", m) is `while len(sample) < m: sample = np.tile(sample, 2)` (m = 10 s); start_high: the window
+# starts at random.randint(0, start_high), 0 = at the first sample, nothing drawn; n_samples: the window; resize: np.resize of
+# the log spectrogram, None = none.  (CramedDataset.py:60-66 / 155-163, AVEDataset.py:81-88, KSDataset.py:139-149,
+# VGGSoundDataset.py:112-122, Kinect400.py:120-129, Audioset.py:140-153.)
+AUDIO_STAGES = {
+    "CREMAD": dict(rate=22050, n_samples=66150, tiling=("times", 3), start_high=0, n_fft=512, hop_length=353, resize=None),
+    "CREMAD_swin": dict(rate=22050, n_samples=66150, tiling=("times", 3), start_high=0, n_fft=512, hop_length=353, resize=(224, 224)),
+    "AVE": dict(rate=22050, n_samples=66150, tiling=("times", 3), start_high=0, n_fft=512, hop_length=256, resize=(224, 224)),
+    "KineticSound": dict(rate=16000, n_samples=80000, tiling=("double", 160000), start_high=80000, n_fft=256, hop_length=128, resize=None),
+    "VGGSound": dict(rate=16000, n_samples=80000, tiling=("double", 160000), start_high=80000, n_fft=256, hop_length=128, resize=None),
+    "kinect400": dict(rate=16000, n_samples=128000, tiling=("double", 160000), start_high=32000, n_fft=256, hop_length=128, resize=None),
+    "Audioset": dict(rate=16000, n_samples=80000, tiling=("double", 160000), start_high=80000, n_fft=512, hop_length=256, resize=(224, 224)),
+}
+
+
+def wave_limit(length, tiling):
+    """The length of a clip of `length` samples after a dataset's tiling (AUDIO_STAGES[name]["tiling"])."""
+    kind, arg = tiling
+    length = int(length)
+    if length < 1:
+        raise ValueError(f"gdl: a clip of {length} samples cannot be tiled")
+    if kind == "times":
+        return length * int(arg)
+    if kind == "double":
+        while length < int(arg):
+            length *= 2
+        return length
+    raise ValueError(f"gdl: unknown tiling rule {tiling!r}")
+
+
+def random_wave_starts(n, high, generator=None):
+    """n window starts, each uniform in [0, high] with `high` included, like the datasets' random.randint(0, high); int64 [n] on
+    the host.  One torch.randint call on `generator` (torch's global RNG if None): the distribution is the reference's, the stream
+    of Python's Mersenne Twister that random.randint reads is not reproduced.  high = 0 draws nothing."""
+    if high < 0:
+        raise ValueError(f"gdl: the largest start {high} must not be negative")
+    if high == 0:
+        return torch.zeros(n, dtype=torch.int64)
+    return torch.randint(0, int(high) + 1, (n,), generator=generator, dtype=torch.int64)
+
+
+def wave_descriptors(clips_meta, starts, limits, n_samples):
+    """The host half of wave_log_spectrogram: checks the windows and lays the clips out in one packed buffer.  clips_meta:
+    [(len, channels, format)] with len in samples per channel and format GDL_WAVE_F32 / GDL_WAVE_S16 (or torch.float32 /
+    torch.int16); starts, limits: one integer per clip.  Returns (desc, nbytes): the int64 [B, 6] table gdl_wave_logspec reads
+    (byte offset, len, channels, format, start, limit) and the length of the packed buffer, every clip starting on a dword.
+    Raises ValueError for len < 1, channels other than 1 or 2, an unknown format, a start below 0 and a window that ends past
+    the tiled length, start + n_samples > limit: the reference would cut a shorter window there and yield a spectrogram of
+    another shape, which its DataLoader cannot batch."""
+    n_samples = int(n_samples)
+    starts = torch.as_tensor(starts, dtype=torch.int64, device="cpu").reshape(-1).tolist()
+    limits = torch.as_tensor(limits, dtype=torch.int64, device="cpu").reshape(-1).tolist()
+    if len(clips_meta) == 0 or len(starts) != len(clips_meta) or len(limits) != len(clips_meta):
+        raise ValueError(f"gdl: {len(clips_meta)} clips need as many starts and limits, not {len(starts)} and {len(limits)}")
+    if n_samples < 1:
+        raise ValueError(f"gdl: a window of {n_samples} samples")
+    rows, offset = [], 0
+    for i, ((length, channels, fmt), start, limit) in enumerate(zip(clips_meta, starts, limits)):
+        fmt = _WAVE_FORMATS.get(fmt, fmt)
+        length, channels = int(length), int(channels)
+        if fmt not in _WAVE_BYTES:
+            raise ValueError(f"gdl: clip {i} has format {fmt!r}; GDL_WAVE_F32 (float32) or GDL_WAVE_S16 (int16)")
+        if length < 1 or length >= 1 << 31:
+            raise ValueError(f"gdl: clip {i} has {length} samples")
+        if channels not in (1, 2):
+            raise ValueError(f"gdl: clip {i} has {channels} channels; one or two")
+        if start < 0:
+            raise ValueError(f"gdl: clip {i} starts its window at {start}")
+        if start + n_samples > limit or limit >= 1 << 31:
+            raise ValueError(f"gdl: the window [{start}, {start + n_samples}) of clip {i} does not lie inside its tiled length {limit} "
+                             "(< 2^31): the reference would yield a shorter spectrogram here")
+        rows.append([offset, length, channels, fmt, start, limit])
+        offset += (length * channels * _WAVE_BYTES[fmt] + 3) // 4 * 4
+    return torch.tensor(rows, dtype=torch.int64), offset
+
+
+def _is_packed(clips):
+    return isinstance(clips, tuple) and len(clips) == 2 and isinstance(clips[1], torch.Tensor) and clips[1].dtype == torch.int64
+
+
+def _clip_meta(c):
+    if not isinstance(c, torch.Tensor) or not c.is_cuda or c.dtype not in _WAVE_FORMATS or c.dim() not in (1, 2):
+        raise ValueError("gdl: clips must be int16 or float32 device tensors [len] or [len, channels], or a (packed, desc) pair")
+    return (int(c.shape[0]), 1 if c.dim() == 1 else int(c.shape[1]), _WAVE_FORMATS[c.dtype])
+
+
+def pack_clips(clips):
+    """A list of clips as one packed device buffer: (packed uint8 tensor, [(len, channels, format)]).  Every clip starts on a
+    dword, at the offsets wave_descriptors gives.  A dataset that lives on the device does this once and then passes
+    (packed, desc) to wave_log_spectrogram / stage_audio."""
+    clips = list(clips)
+    meta = [_clip_meta(c) for c in clips]
+    parts = []
+    for c in clips:
+        raw = c.contiguous().reshape(-1).view(torch.uint8)
+        parts.append(raw)
+        if raw.numel() % 4:
+            parts.append(torch.zeros(4 - raw.numel() % 4, dtype=torch.uint8, device=c.device))
+    return torch.cat(parts), meta  # (a fresh allocation is aligned)
+
+
+def wave_log_spectrogram(clips, n_samples, starts, limits, n_fft, hop_length, pad_mode="constant", resize=None, return_wave=False,
+                         out=None):
+    """From decoded clips to the datasets' log spectrograms in one launch: sample p of clip b's window is
+    clip(mono_b[(starts[b] + p) mod len_b], -1, 1) for 0 <= p < n_samples -- the reference's np.tile(...)[start:start + n_samples]
+    for either tiling rule, as long as starts[b] + n_samples <= limits[b], the tiled length -- with mono = x / 32768 for int16
+    and the mean of the channels for stereo (librosa.load); then log_spectrogram of that window, bit for bit; then
+    np.resize(spec, resize) if `resize` is given (a flat re-layout: the spectrogram's elements repeated or cut off in row-major
+    order).
+
+    clips: a list of device tensors, each int16 or float32 and [len] or [len, channels] with one or two channels (they are
+    concatenated into one packed buffer), or a (packed, desc) pair for a dataset that already lives on the device: `packed` any
+    contiguous device tensor holding the clips at the byte offsets of `desc`, the int64 [B, 6] table of wave_descriptors.  With
+    the pair nothing is concatenated; starts / limits replace the table's columns where given (one small upload), and with both
+    None a table that is on the device is used as it is.
+    Resampling is not part of this: a clip is at its dataset's rate.  The 16 kHz datasets' wavs are stored at 16 kHz as 16-bit
+    PCM and go in as int16; clips of the 22050 Hz datasets (CREMA-D, AVE) are resampled on the host and go in as float32.
+    Returns float32 [B, n_fft//2+1, 1 + n_samples//hop_length], or [B, *resize]; with return_wave=True a pair of that and the
+    staged windows, float32 [B, n_samples]."""
+    if pad_mode not in PAD_MODES:
+        raise ValueError(f"gdl: pad_mode must be one of {sorted(PAD_MODES)}, not {pad_mode!r}")
+    n_samples = int(n_samples)
+    if _is_packed(clips):
+        packed, desc = clips
+        if not isinstance(packed, torch.Tensor) or not packed.is_cuda or not packed.is_contiguous():
+            raise ValueError("gdl: packed must be a contiguous device tensor")
+        if desc.dim() != 2 or desc.shape[1] != 6 or desc.shape[0] < 1:
+            raise ValueError("gdl: desc must be the int64 [B, 6] table of wave_descriptors")
+        dev = packed.device
+        if starts is not None or limits is not None or not desc.is_cuda:
+            host = desc.cpu()
+            starts = host[:, 4] if starts is None else starts
+            limits = host[:, 5] if limits is None else limits
+            checked, _ = wave_descriptors([tuple(r) for r in host[:, 1:4].tolist()], starts, limits, n_samples)
+            checked[:, 0] = host[:, 0]
+            desc = checked
+        desc = desc.to(dev).contiguous()
+    else:
+        clips = list(clips)
+        if not clips:
+            raise ValueError("gdl: no clips")
+        packed, meta = pack_clips(clips)
+        dev = packed.device
+        desc, nbytes = wave_descriptors(meta, starts, limits, n_samples)
+        assert packed.numel() == nbytes
+        desc = desc.to(dev)
+    B = desc.shape[0]
+    frames = L.load().gdl_logspec_frames(n_samples, hop_length)
+    rh, rw = (0, 0) if resize is None else _size2(resize)
+    shape = (B, n_fft // 2 + 1, frames) if resize is None else (B, rh, rw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"gdl: out must be a contiguous float32 device tensor {list(shape)}")
+    wave = torch.empty(B, n_samples, dtype=torch.float32, device=dev) if return_wave else None
+    L.call("gdl_wave_logspec", L.ptr(packed), packed.numel() * packed.element_size(), L.ptr(desc), B, n_samples, n_fft, hop_length,
+           PAD_MODES[pad_mode], rh, rw, L.ptr(wave), L.ptr(out), L.cur_stream())
+    return (out, wave) if return_wave else out
+
+
+def stage_audio(clips, dataset, starts=None, generator=None, pad_mode="constant", return_wave=False, out=None):
+    """The audio half of a reference dataset's __getitem__ by name (AUDIO_STAGES), for a batch: tiled length by the dataset's
+    rule, a window start per clip -- `starts`, or drawn by random_wave_starts from `generator` (torch's global RNG if None) in
+    the dataset's range -- the window, the dataset's STFT and its np.resize.  The reference draws the window in test mode as well,
+    so there is no train flag.  The draws have the reference's distribution; the stream of Python's Mersenne Twister behind its
+    random.randint is not reproduced.  clips, the rest and the result as wave_log_spectrogram; the clips are at the dataset's
+    rate (AUDIO_STAGES[dataset]["rate"]): nothing is resampled here, and the 22050 Hz datasets pass float32 clips that the host
+    has resampled."""
+    if dataset not in AUDIO_STAGES:
+        raise ValueError(f"gdl: no audio stage for dataset {dataset!r}; one of {sorted(AUDIO_STAGES)}")
+    st = AUDIO_STAGES[dataset]
+    if _is_packed(clips):
+        if not isinstance(clips[0], torch.Tensor) or not clips[0].is_cuda:
+            raise ValueError("gdl: packed must be a contiguous device tensor")
+        lengths = clips[1][:, 1].cpu().tolist()
+    else:
+        clips = list(clips)
+        lengths = [_clip_meta(c)[0] for c in clips]
+    limits = [wave_limit(n, st["tiling"]) for n in lengths]
+    if starts is None:
+        starts = random_wave_starts(len(lengths), st["start_high"], generator)
+    return wave_log_spectrogram(clips, st["n_samples"], starts, limits, st["n_fft"], st["hop_length"], pad_mode, st["resize"],
+                                return_wave, out)
 
 
 def normalize_frames(frames_u8, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):

@@ -436,9 +436,30 @@ GDL_API int gdl_eval_count(const float* out, const float* out_a, const float* ou
  *   gdl_logspec: clip to [-1, 1], librosa.stft(n_fft, hop_length) with librosa's defaults (periodic Hann window of
  *     n_fft samples, center=True), log(|X| + 1e-7)  (dataset/CramedDataset.py:62-66: n_fft 512, hop 353;
  *     KSDataset.py:144-149 / VGGSoundDataset.py:117-122: 256 / 128).  wave: float32 [B][n_samples] (already resampled
- *     and tiled / cropped to its fixed length by the host); out: float32 [B][n_fft/2+1][gdl_logspec_frames()], the
+ *     and tiled / cropped to its fixed length by the host; gdl_wave_logspec below does the staging too); out: float32 [B][n_fft/2+1][gdl_logspec_frames()], the
  *     tensor the DataLoader yields.  pad_mode: how the n_fft/2 samples either side are made up -- librosa >= 0.10
  *     pads with zeros (GDL_PAD_CONSTANT), older releases reflect (GDL_PAD_REFLECT); the reference does not pin a version.
+ *   gdl_wave_logspec: what the datasets do between the decoded file and that spectrogram, and the spectrogram, in one launch:
+ *     the decode scale of 16-bit PCM (x / 32768, soundfile's float read), librosa.load's mono=True mix-down (np.mean over the
+ *     channels: (l + r) / 2), the tiling (np.tile(samples, 3) of CREMA-D / AVE, the `while len / rate < 10: tile(., 2)` of the
+ *     16 kHz datasets), the window [start, start + n_samples), the clip to [-1, 1], gdl_logspec's transform, and, where a
+ *     dataset has it, np.resize(spectrogram, (out_h, out_w))  (KSDataset.py:139-149, VGGSoundDataset.py:112-122,
+ *     Kinect400.py:120-129, Audioset.py:140-153, CramedDataset.py:60-66 / 155-163, AVEDataset.py:81-88).  Both tilings are the
+ *     periodic extension of the clip, staged[p] = mono[(start + p) mod len], 0 <= p < n_samples, as long as the window ends
+ *     inside the tiled length `limit`; the padding of the STFT (zeros or reflection) is applied to that staged window.
+ *     src: the decoded clips packed in one device buffer of src_bytes bytes (4-byte aligned, every clip starting on a 4-byte
+ *     boundary), each float32 (GDL_WAVE_F32) or int16 (GDL_WAVE_S16), one or two channels interleaved as files store them.
+ *     desc: int64 [B][6] in device memory (8-byte aligned),
+ *       { byte offset of the clip in src, len (samples per channel), channels, format, start, limit }.
+ *     out_h = out_w = 0: out is float32 [B][n_fft/2+1][gdl_logspec_frames(n_samples, hop)], bit-identical to gdl_logspec of
+ *     the staged window (the two kernels share the transform's device code).  Otherwise out is float32 [B][out_h][out_w]
+ *     under np.resize's rule, a flat re-layout and not an interpolation: out.flat[i] = spec.flat[i mod (bins * frames)].
+ *     wave_out: NULL, or float32 [B][n_samples] that receives the staged, clipped window.
+ *     Resampling is not done here: a clip is at the rate its dataset works at (the 16 kHz datasets' files are; CREMA-D and
+ *     AVE clips are resampled to 22050 Hz by the host and passed as float32).
+ *     A sample whose clip does not lie inside src (or starts off a 4-byte boundary), or with len < 1 or >= 2^31, channels not
+ *     1 or 2, an unknown format, start < 0 or not start + n_samples <= limit < 2^31, is written as NaN -- its out and its
+ *     wave_out row -- and nothing of it is read.  Limits: B <= 65535, n_samples < 2^31 - 4096, out_h * out_w < 2^31.
  *   gdl_frames_normalize: transforms.ToTensor() + Normalize(mean, std) (CramedDataset.py:77-81): uint8 [n_img][H][W][3]
  *     -> float32 [n_img][3][H][W], ((x / 255) - mean[c]) / std[c]; mean / std: 3 host floats each.
  *   gdl_frames_resized_crop: the datasets' whole visual transform in one launch -- training: RandomResizedCrop(size),
@@ -468,6 +489,10 @@ GDL_API int gdl_eval_count(const float* out, const float* out_a, const float* ou
 #define GDL_PAD_REFLECT 1
 GDL_API int gdl_logspec_frames(int n_samples, int hop);
 GDL_API int gdl_logspec(const float* wave, int B, int n_samples, int n_fft, int hop, int pad_mode, float* out, void* stream);
+#define GDL_WAVE_F32 0
+#define GDL_WAVE_S16 1
+GDL_API int gdl_wave_logspec(const void* src, size_t src_bytes, const int64_t* desc, int B, int n_samples, int n_fft, int hop,
+                             int pad_mode, int out_h, int out_w, float* wave_out, float* out, void* stream);
 GDL_API int gdl_frames_normalize(const uint8_t* frames, int64_t n_img, int H, int W, const float* mean, const float* std,
                                  float* out, void* stream);
 GDL_API int gdl_frames_resized_crop_box_ok(int box_h, int box_w, int out_h, int out_w);
