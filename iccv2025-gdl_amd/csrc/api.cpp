@@ -292,6 +292,22 @@ int gdl_head_cls_ce(const float* f, const float* W, const float* b, const int64_
     GDL_REQUIRE(width == 512, "head_cls_ce: feature width %d (the classifier is built for 512)", width);
     return head_cls_ce(f, W, b, labels, scale, out, loss, dlogits, df, B, n_classes, (hipStream_t)stream);
 }
+size_t gdl_linprobe_workspace_bytes(int B, int n_classes) { return linprobe_ws_bytes(B, n_classes); }
+int gdl_linprobe_epoch(const float* bank, const int64_t* labels, int64_t N, const int32_t* order, int steps, int B, float* W,
+                       float* b, float* mW, float* mb, int n_classes, float lr, float momentum, float weight_decay, float max_norm,
+                       double* loss_acc, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(n_classes >= 1 && n_classes <= 512, "linprobe_epoch: n_classes must be in [1, 512] (Linear(512, n)), got %d", n_classes);
+    GDL_REQUIRE(B >= 1 && steps >= 0 && N >= 1, "linprobe_epoch: B = %d (>= 1), steps = %d (>= 0), N = %lld (>= 1)", B, steps, (long long)N);
+    GDL_REQUIRE(bank && labels && W && b && mW && mb && loss_acc && ws && (order || steps == 0), "linprobe_epoch: null argument");
+    GDL_REQUIRE((((uintptr_t)W | (uintptr_t)mW | (uintptr_t)ws) & 15) == 0 && ((uintptr_t)loss_acc & 7) == 0,
+                "linprobe_epoch: W, mW and ws must be 16-byte aligned, loss_acc 8-byte aligned");
+    if (ws_bytes < linprobe_ws_bytes(B, n_classes)) {
+        set_error("linprobe_epoch: workspace %zu < %zu", ws_bytes, linprobe_ws_bytes(B, n_classes));
+        return GDL_ERR_WORKSPACE;
+    }
+    return linprobe_epoch(bank, labels, N, order, steps, B, W, b, mW, mb, n_classes, lr, momentum, weight_decay, max_norm, loss_acc,
+                          ws, (hipStream_t)stream);
+}
 size_t gdl_feature_diversity_workspace_bytes(int n_img) { return feature_diversity_ws_bytes(n_img); }
 int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int P, int C, float* per_image, float* mean_out,
                           float* accum, void* ws, size_t ws_bytes, void* stream) {

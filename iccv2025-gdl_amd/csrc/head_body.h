@@ -1,7 +1,8 @@
 // head_body.h -- one sample's "logits -> cross-entropy gradient -> feature gradient" on a 1024-thread block, and the dot and
 // walk helpers it is made of.  head_uni_dfeat_kernel (head.hip, the DGL step) IS this body; head_cls_ce_kernel (head_cls.hip,
 // the unimodal step) is this body with its two stores compiled in (STORE), plus the sample's loss term and the loss sum;
-// head_cls_fwd_kernel / head_cls_dfeat_kernel use the helpers.  Every sum has ONE order and ONE spelling (explicit fmaf: the bits do not depend on the contraction default):
+// head_cls_fwd_kernel / head_cls_dfeat_kernel use the helpers; linprobe_ce_kernel (linprobe.hip, the linear probe's fit) is the
+// body's first part, head_ce_logits, on a row gathered from a feature bank.  Every sum has ONE order and ONE spelling (explicit fmaf: the bits do not depend on the contraction default):
 //   a logit      : lane l of a wave adds W[j][l + 64 i] * f[l + 64 i] for i = 0 .. ND-1 (fmaf chain), xor butterfly 32 .. 1, + b[j]
 //   softmax / CE : softmax_ce_block's (head.hip) -- max (exact in any order), expf(l - max) summed in class order,
 //                  lse = max + logf(sum), dlogits = scale * (expf(l - lse) - onehot) / B
@@ -60,23 +61,23 @@ struct alignas(16) HeadBodyLds {
     float lse;
 };
 
-// Sample b = blockIdx.x of a grid of B blocks of 1024 threads; n <= HB_MAXN.  16 waves per sample and no serial walk beyond the
-// sums whose order is the contract: the classes go round the 16 waves two at a time, max and exp are evaluated by all threads
-// (max is exact in any order; the exponentials are the same values) and only their SUM is walked in class order by one thread;
-// df[b] is written by the threads < 64 ND in strides of 1024, so behind the last barrier the other waves are free.
-// STORE: the logits and their gradient also go to out[B, n] / dlogits[B, n], from the loops that have them in a register (the
-// max and the dl loop); without it the two pointers are not read.
+// One sample's logits, softmax and logit gradient on a 1024-thread block, up to and including the last barrier: fb the sample's
+// features, lab_p its label, out_b / dl_b its rows of out[B, n] / dlogits[B, n] (STORE only); B the divisor of the mean.  16 waves
+// per sample and no serial walk beyond the sums whose order is the contract: the classes go round the 16 waves two at a time,
+// max and exp are evaluated by all threads (max is exact in any order; the exponentials are the same values) and only their SUM
+// is walked in class order by one thread.  Leaves s.lg, s.dl and s.lse for the caller.  head_ce_body below is this plus the
+// feature gradient; linprobe_ce_kernel (linprobe.hip) is this on a gathered row.
+// STORE: the logits and their gradient also go to out_b / dl_b, from the loops that have them in a register (the max and the dl
+// loop); without it the two pointers are not read.
 // Returns the sample's label, -1 for a class index outside [0, n) (a device assert in the reference's CrossEntropyLoss): no
 // one-hot term then.
 template <int ND, bool STORE>
-__device__ __forceinline__ int head_ce_body(HeadBodyLds& s, const float* __restrict__ f, const float* __restrict__ W, int ldw,
-                                            const float* __restrict__ bias, const int64_t* __restrict__ labels, float scale,
-                                            float* __restrict__ out, float* __restrict__ dlogits, float* __restrict__ df, int B,
-                                            int n) {
-    constexpr int D = 64 * ND;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__device__ __forceinline__ int head_ce_logits(HeadBodyLds& s, const float* __restrict__ fb, const float* __restrict__ W, int ldw,
+                                              const float* __restrict__ bias, const int64_t* __restrict__ lab_p, float scale,
+                                              float* __restrict__ out_b, float* __restrict__ dl_b, int B, int n) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float fv[ND];
-    head_load_feat<ND>(f + (size_t)b * D, lane, fv);
+    head_load_feat<ND>(fb, lane, fv);
     for (int j = wave; j < n; j += 2 * HB_NW) {
         const int j2 = j + HB_NW;
         float pa, pb;
@@ -91,7 +92,7 @@ __device__ __forceinline__ int head_ce_body(HeadBodyLds& s, const float* __restr
         float mx = -INFINITY;
         for (int j = threadIdx.x; j < n; j += 1024) {
             const float l = s.lg[j];
-            if (STORE) out[(size_t)b * n + j] = l;
+            if (STORE) out_b[j] = l;
             mx = fmaxf(mx, l);
         }
 #pragma unroll
@@ -110,15 +111,29 @@ __device__ __forceinline__ int head_ce_body(HeadBodyLds& s, const float* __restr
         s.lse = mx + logf(se);
     }
     __syncthreads();
-    const long lab64 = (long)labels[b];
+    const long lab64 = (long)lab_p[0];
     const int lab = (lab64 >= 0 && lab64 < n) ? (int)lab64 : -1;
     const float lse = s.lse;
     for (int j = threadIdx.x; j < n; j += 1024) {
         const float d = scale * (expf(s.lg[j] - lse) - (j == lab ? 1.f : 0.f)) / (float)B;
         s.dl[j] = d;
-        if (STORE) dlogits[(size_t)b * n + j] = d;
+        if (STORE) dl_b[j] = d;
     }
     __syncthreads();  // (the last barrier: from here on the waves part ways)
+    return lab;
+}
+
+// Sample b = blockIdx.x of a grid of B blocks of 1024 threads; n <= HB_MAXN: head_ce_logits on row b, then df[b], written by the
+// threads < 64 ND in strides of 1024, so behind the last barrier the other waves are free.  STORE and the return value: as above.
+template <int ND, bool STORE>
+__device__ __forceinline__ int head_ce_body(HeadBodyLds& s, const float* __restrict__ f, const float* __restrict__ W, int ldw,
+                                            const float* __restrict__ bias, const int64_t* __restrict__ labels, float scale,
+                                            float* __restrict__ out, float* __restrict__ dlogits, float* __restrict__ df, int B,
+                                            int n) {
+    constexpr int D = 64 * ND;
+    const int b = blockIdx.x;
+    const int lab = head_ce_logits<ND, STORE>(s, f + (size_t)b * D, W, ldw, bias, labels + b, scale,
+                                              STORE ? out + (size_t)b * n : nullptr, STORE ? dlogits + (size_t)b * n : nullptr, B, n);
     for (int i = threadIdx.x; i < D; i += 1024) df[(size_t)b * D + i] = head_df_walk(s.dl, W, ldw, i, n);
     return lab;
 }

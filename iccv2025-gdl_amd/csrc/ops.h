@@ -168,6 +168,11 @@ int head_cls_fwd(const float* f, const float* W, const float* b, float* out, int
 int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, float* dW, float* db, int B, int n, hipStream_t st);
 int head_cls_ce(const float* f, const float* W, const float* b, const int64_t* labels, float scale, float* out, float* loss,
                 float* dlogits, float* df, int B, int n, hipStream_t st);
+// linprobe.hip: one epoch of the linear probe's fused fit (three launches per step, the loop over the steps in C++)
+size_t linprobe_ws_bytes(int B, int n);
+int linprobe_epoch(const float* bank, const int64_t* labels, int64_t N, const int32_t* order, int steps, int B, float* W, float* b,
+                   float* mW, float* mb, int n, float lr, float mu, float wd, float max_norm, double* loss_acc, void* ws,
+                   hipStream_t st);
 // head_mtl.hip: the one-launch junction of the step whose fused loss reaches the encoders (concat / sum DGL head, un-detached)
 size_t head_mtl_ce_ws_bytes(int B);
 int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,

@@ -12,11 +12,16 @@ def __getattr__(name):
     """`gdl.DGLTrainer` / `gdl.UnimodalTrainer`: the two runners, and `gdl.feature_diversity`, main.py's per-step monitor on a
     feature map, and `gdl.journal`, the step journal's module (`gdl.journal.COLUMNS`), and the device-side waveform staging of
     gdl.data (`gdl.stage_audio`, `gdl.wave_log_spectrogram`, `gdl.wave_descriptors`, `gdl.pack_clips`, `gdl.wave_limit`,
-    `gdl.random_wave_starts`, `gdl.AUDIO_STAGES`) -- imported on first use (they import torch)."""
+    `gdl.random_wave_starts`, `gdl.AUDIO_STAGES`), and the linear probe of gdl.probe (`gdl.extract_features`, `gdl.FeatureBank`,
+    `gdl.LinearProbe`, `gdl.probe_order`, `gdl.multistep_lr`) -- imported on first use (they import torch)."""
     if name in ("stage_audio", "wave_log_spectrogram", "wave_descriptors", "pack_clips", "wave_limit", "random_wave_starts", "AUDIO_STAGES"):
         from . import data
 
         return getattr(data, name)
+    if name in ("extract_features", "FeatureBank", "LinearProbe", "probe_order", "multistep_lr"):
+        from . import probe
+
+        return getattr(probe, name)
     if name == "journal":
         import importlib
 

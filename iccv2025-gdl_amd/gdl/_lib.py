@@ -109,6 +109,8 @@ SIGNATURES = {
     "gdl_head_cls_ce": ("i", "pppp" + "f" + "pppp" + "iii" + "p"),
     "gdl_head_mtl_ce_workspace_bytes": ("z", "i"),
     "gdl_head_mtl_ce": ("i", "pppp" + "i" + "pp" + "i" + "p" + "fi" + "ppp" + "p" + "ppp" + "pp" + "ii" + "pz" + "p"),
+    "gdl_linprobe_workspace_bytes": ("z", "ii"),
+    "gdl_linprobe_epoch": ("i", "ppl" + "pii" + "pppp" + "i" + "ffff" + "p" + "pz" + "p"),
     "gdl_feature_diversity_workspace_bytes": ("z", "i"),
     "gdl_feature_diversity": ("i", "p" + "iiiii" + "ppp" + "pz" + "p"),
     "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),

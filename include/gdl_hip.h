@@ -700,6 +700,30 @@ GDL_API int gdl_journal_append(void* journal, int64_t capacity, const float* los
                                const float* out_a, const float* out_v, int64_t n_logits, const float* div_a, const float* div_v,
                                const float* ogm, void* stream);
 
+/* ------------------------------------------------------------------ linear probe of a frozen encoder
+ * One epoch of the linear probe's fit: main.py's unimodal step with the encoder removed, on features that are already on the
+ * device.  bank [N][512] float32 (the pooled features of an eval-mode encoder), labels [N] int64, order [steps][B] int32 (device):
+ * step s trains on the rows order[s][0 .. B-1].  Per step
+ *   out = f W^T + b;  loss = mean CE(out, y);  clip_grad_norm_({dW, db}, max_norm);  SGD(lr, momentum, weight_decay)
+ * with the logits and the softmax of gdl_head_cls_ce (the same device functions), the gradient sums in sample order, and the
+ * clip and the update of gdl_optim_grad_stats / gdl_optim_sgd_step: the norm accumulated in double, coef = min(1, max_norm /
+ * (norm + 1e-6)), d = coef g + wd p, m = mu m + d, p -= lr m.  W [n][512], b [n] and their momentum buffers mW, mb (zero before
+ * the first epoch) are updated in place; loss_acc[0] += the sum of the steps' mean losses (each a float, widened), loss_acc[1] +=
+ * steps -- the caller zeroes the two doubles where an epoch's mean should start.
+ * The loop over the steps runs inside the call: three launches per step, ordered by the stream alone -- no block waits for
+ * another, no floating-point atomic, every sum in one fixed order: two calls from the same state and order table give the same
+ * bits.  Nothing is allocated and nothing synchronises.  `ws` (gdl_linprobe_workspace_bytes, 16-byte aligned) is scratch: it
+ * holds no counter and needs no zeroing; calls sharing one `ws` must be ordered on one stream.
+ * A label outside [0, n) gives no one-hot term and a NaN loss, as in gdl_softmax_ce.  An order index outside [0, N) never reads
+ * outside the bank: the step uses row 0 in its place and its loss is NaN (check the table on the host: gdl.LinearProbe does).
+ * GDL_ERR_ARG, with a message and without a launch or a write: n_classes outside [1, 512], B < 1, steps < 0, N < 1, a NULL
+ * pointer (order may be NULL with steps = 0), W / mW / ws not 16-byte aligned; GDL_ERR_WORKSPACE: ws_bytes too small.
+ * B need not divide N.  gdl_linprobe_workspace_bytes: 0 for arguments the epoch would refuse. */
+GDL_API size_t gdl_linprobe_workspace_bytes(int B, int n_classes);
+GDL_API int gdl_linprobe_epoch(const float* bank, const int64_t* labels, int64_t N, const int32_t* order, int steps, int B,
+                               float* W, float* b, float* mW, float* mb, int n_classes, float lr, float momentum,
+                               float weight_decay, float max_norm, double* loss_acc, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ measurement tap
  * Optional HIP-event timing of every kernel launch (off by default).  While enabled, each
  * launcher records an event pair on the launching stream and its algorithmic work (flops for
