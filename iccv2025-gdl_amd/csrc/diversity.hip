@@ -15,13 +15,13 @@
 //      (ceil(P/16) + 1) / 2 tiles, dealt round-robin to the four waves, accumulators in registers for the whole image)
 //      take their 8 exact-f32 MFMAs (mfma_f32_16x16x4f32) per tile and chunk
 //   3. 1 / sqrt(G_pp) from the diagonal tiles, then sum (G_pq / sqrt(G_pp G_qq))^2 over the tiles, off-diagonal tiles twice
-// The mean over images: head_mtl_ce_kernel's ticket pattern -- d published with an agent-scope store, the block that draws the
-// last ticket folds the n_img terms in ONE fixed order (256 partial sums taking i, i + 256, ... in turn, then the tree), writes
-// mean_out[0], adds to the epoch accumulator and hands the counter back at zero.  No floating-point atomic; nothing depends on
-// which block comes last.
+// The mean over images: the ticket protocol of ticket.h -- d published with an agent-scope store, the block that draws the last
+// ticket folds the n_img terms in ticket_fold256's order, writes mean_out[0], adds to the epoch accumulator and hands the
+// counter back at zero.
 #include "common.h"
 #include "ops.h"
 #include "prof.h"
+#include "ticket.h"
 
 namespace gdl {
 
@@ -260,19 +260,11 @@ __global__ __launch_bounds__(DV_NT) void feature_diversity_kernel(const T* __res
             const float d = (float)(DV_C - 1) * sqrtf(tot) / ((float)P * (float)P);
             if (per_image) per_image[img] = d;
             st_agent(part + img, d);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(n_img - 1);
+            last = ticket_draw(cnt, n_img);
         }
         last = __shfl(last, 0);
         if (last) {
-            float a[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int i0 = lane; i0 < n_img; i0 += 256)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (i0 + 64 * q < n_img) a[q] += __hip_atomic_load(part + i0 + 64 * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            float m = (a[0] + a[2]) + (a[1] + a[3]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o);
+            float m = ticket_fold256(part, n_img, lane);
             if (lane == 0) {
                 m = m / (float)n_img;
                 mean_out[0] = m;
@@ -280,7 +272,7 @@ __global__ __launch_bounds__(DV_NT) void feature_diversity_kernel(const T* __res
                     accum[0] += m;
                     accum[1] += 1.f;
                 }
-                __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ticket_hand_back(cnt);
             }
         }
     }

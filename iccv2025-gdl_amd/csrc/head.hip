@@ -11,6 +11,7 @@
 #include "common.h"
 #include "head_body.h"
 #include "prof.h"
+#include "ticket.h"
 
 namespace gdl {
 
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
         float pa = 0.f, pv = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            pa += wx[lane + 64 * i] * xv[i];
+            pa += wx[lane + 64 * i] * xv[i];  // (the parent's spelling: as fmaf the same instructions come out in other registers)
             pv += wy[lane + 64 * i] * yv[i];
         }
 #pragma unroll
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(256) void head_bwd_feat_kernel(HeadW w, const float
         for (int j = 0; j < n; ++j) {
             float g = gu ? gu[(size_t)b * n + j] : 0.f;
             if (out_reaches_xy && g_out) g += g_out[(size_t)b * n + j];
-            s += g * W[(size_t)j * w.ldw + fi];
+            s = fmaf(g, W[(size_t)j * w.ldw + fi], s);
         }
         if (is_y)
             dy[(size_t)b * HD + fi] = s;
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void head_bwd_w_kernel(const float* __restrict
         }
         __syncthreads();
 #pragma unroll 8
-        for (int b = 0; b < nb; ++b) s += gs[b] * feat[(size_t)(b0 + b) * HD + fi];
+        for (int b = 0; b < nb; ++b) s = fmaf(gs[b], feat[(size_t)(b0 + b) * HD + fi], s);
     }
     (is_y ? dWy : dWx)[(size_t)j * ldw + fi] = s;
     if (blockIdx.y == 0 && threadIdx.x == 0) {
@@ -199,21 +200,21 @@ __global__ __launch_bounds__(256) void head_xy_fwd_kernel(const float* __restric
         if (reg) {
 #pragma unroll
             for (int v = 0; v < MAXV; ++v)
-                if (lane + 64 * v < dxw) pa += w[lane + 64 * v] * xs[v];
+                if (lane + 64 * v < dxw) pa = fmaf(xs[v], w[lane + 64 * v], pa);
 #pragma unroll
             for (int v = 0; v < MAXV; ++v)
-                if (lane + 64 * v < dyw) pv += w[dxw + lane + 64 * v] * ys[v];
+                if (lane + 64 * v < dyw) pv = fmaf(ys[v], w[dxw + lane + 64 * v], pv);
 #pragma unroll
             for (int v = 0; v < MAXV; ++v)
-                if (lane + 64 * v < dxw) qa += w2[lane + 64 * v] * xs[v];
+                if (lane + 64 * v < dxw) qa = fmaf(xs[v], w2[lane + 64 * v], qa);
 #pragma unroll
             for (int v = 0; v < MAXV; ++v)
-                if (lane + 64 * v < dyw) qv += w2[dxw + lane + 64 * v] * ys[v];
+                if (lane + 64 * v < dyw) qv = fmaf(ys[v], w2[dxw + lane + 64 * v], qv);
         } else {
-            for (int i = lane; i < dxw; i += 64) pa += w[i] * x[(size_t)b * dxw + i];
-            for (int i = lane; i < dyw; i += 64) pv += w[dxw + i] * y[(size_t)b * dyw + i];
-            for (int i = lane; i < dxw; i += 64) qa += w2[i] * x[(size_t)b * dxw + i];
-            for (int i = lane; i < dyw; i += 64) qv += w2[dxw + i] * y[(size_t)b * dyw + i];
+            for (int i = lane; i < dxw; i += 64) pa = fmaf(x[(size_t)b * dxw + i], w[i], pa);
+            for (int i = lane; i < dyw; i += 64) pv = fmaf(y[(size_t)b * dyw + i], w[dxw + i], pv);
+            for (int i = lane; i < dxw; i += 64) qa = fmaf(x[(size_t)b * dxw + i], w2[i], qa);
+            for (int i = lane; i < dyw; i += 64) qv = fmaf(y[(size_t)b * dyw + i], w2[dxw + i], qv);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -254,18 +255,7 @@ __global__ __launch_bounds__(256) void head_xy_bwd_feat_kernel(const float* __re
     if (i >= dxw + dyw) return;
     const bool is_y = i >= dxw;
     const float* g = hxy_g + (is_y ? n : 0);
-    const float* w = W + i;
-    const int ldw = dxw + dyw;
-    float s = 0.f;
-    int j = 0;
-    for (; j + 8 <= n; j += 8) {
-        float q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = w[(size_t)(j + u) * ldw];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += g[j + u] * q[u];
-    }
-    for (; j < n; ++j) s += g[j] * w[(size_t)j * ldw];
+    const float s = head_df_walk(g, W, dxw + dyw, i, n);
     if (is_y)
         dy[(size_t)b * dyw + i - dxw] = s;
     else
@@ -284,7 +274,7 @@ __global__ __launch_bounds__(256) void head_xy_bwd_w_kernel(const float* __restr
         for (int b = 0; b < B; ++b) {
             float g = g_out ? g_out[(size_t)b * n + j] : 0.f;
             if (uni_in_dw && gu) g += gu[(size_t)b * n + j];
-            s += g * (is_y ? y[(size_t)b * dyw + i - dxw] : x[(size_t)b * dxw + i]);
+            s = fmaf(g, is_y ? y[(size_t)b * dyw + i - dxw] : x[(size_t)b * dxw + i], s);
         }
         dW[(size_t)j * (dxw + dyw) + i] = s;
     }
@@ -449,8 +439,9 @@ int head_uni_dfeat(const float* f, const float* Wp, int ldw, const float* bp, co
 // ---------------------------------------------------------------- the unimodal scores of OGM / OGM-GE (main.py:286-295)
 // u_a = fa Wa^T + bias_scale ba, u_v = fv Wv^T + bias_scale bv;  prob[b] = {softmax(u_a[b])[label_b], softmax(u_v[b])[label_b]};
 // scores = {sum_b prob[b][0], sum_b prob[b][1]}.  grid = B, a sample per block: the classes go round the 16 waves two at a time
-// (head_dot2), wave 0 / wave 1 then take the audio / visual softmax.  The block that draws the last ticket adds the B
-// probabilities of each modality in sample order (one thread each: a fixed order, no float atomics) and hands the ticket
+// (head_dot2), wave 0 / wave 1 then take the audio / visual softmax and publish the probability (ticket.h: an agent-scope store,
+// waited for in front of the block barrier behind which wave 0 draws the ticket).  The block that draws the last ticket adds
+// the B probabilities of each modality in sample order (one lane each: a fixed order, no float atomics) and hands the ticket
 // counter back at zero.  A label outside [0, n) makes the sample's probabilities -- and with them the scores -- NaN.
 __global__ __launch_bounds__(1024) void head_uni_scores_kernel(const float* __restrict__ fa, const float* __restrict__ fv,
                                                               const float* __restrict__ Wa, const float* __restrict__ Wv, int ldw,
@@ -459,7 +450,6 @@ __global__ __launch_bounds__(1024) void head_uni_scores_kernel(const float* __re
                                                               float* prob, float* __restrict__ scores,
                                                               unsigned int* __restrict__ ticket, int B, int n) {
     __shared__ float lg[2][HB_MAXN];
-    __shared__ unsigned int last;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -489,24 +479,23 @@ __global__ __launch_bounds__(1024) void head_uni_scores_kernel(const float* __re
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
         const long lab64 = (long)labels[b];
-        if (lane == 0) prob[(size_t)b * 2 + wave] = (lab64 >= 0 && lab64 < n) ? expf(l[lab64] - mx) / se : __builtin_nanf("");
-    }
-    __threadfence();  // the two probabilities are visible device-wide before the ticket is drawn
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == (unsigned int)(B - 1);
+        if (lane == 0) {
+            st_agent(prob + (size_t)b * 2 + wave, (lab64 >= 0 && lab64 < n) ? expf(l[lab64] - mx) / se : __builtin_nanf(""));
+            ticket_wait_stores();
+        }
     }
     __syncthreads();
+    if (wave != 0) return;
+    int last = 0;
+    if (lane == 0) last = ticket_draw(ticket, B);
+    last = __shfl(last, 0);
     if (!last) return;
-    __threadfence();
-    if (threadIdx.x < 2) {
-        const volatile float* pr = prob;
+    if (lane < 2) {
         float s = 0.f;
-        for (int i = 0; i < B; ++i) s += pr[(size_t)i * 2 + threadIdx.x];
-        scores[threadIdx.x] = s;
+        for (int i = 0; i < B; ++i) s += ld_agent(prob + (size_t)i * 2 + lane);
+        scores[lane] = s;
     }
-    if (threadIdx.x == 0) *ticket = 0u;
+    if (lane == 0) ticket_hand_back(ticket);
 }
 int head_uni_scores(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
                     float bias_scale, const int64_t* labels, float* prob, float* scores, int B, int n, void* ws, hipStream_t st) {
@@ -537,14 +526,17 @@ __global__ __launch_bounds__(256) void gated_hidden_kernel(const float* __restri
         const float* w = W + (size_t)j * HD;
         float p = 0.f;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) p += w[lane + 64 * i] * v[i];
+        for (int i = 0; i < 8; ++i) p = fmaf(v[i], w[lane + 64 * i], p);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
         if (lane == 0) h[j] = p + bias[j];
     }
 }
-// grid = B: the three logit sets from the hidden vectors
-__global__ __launch_bounds__(256) void gated_out_kernel(const float* __restrict__ hx, const float* __restrict__ hy,
+// grid = B: the logit sets from the hidden vectors.  out = fc_out(sigmoid(gate) * value); UNI: also the unimodal sets of the DGL
+// head (gate = hx, value = hy), x_out from swish(gate) and y_out from swish(value).  Without UNI (the joint head) the fused set
+// alone: per class the same products, lane order and butterfly, so `out` has the same bits in both.
+template <bool UNI>
+__global__ __launch_bounds__(256) void gated_out_kernel(const float* __restrict__ gate, const float* __restrict__ val,
                                                         const float* __restrict__ Wo, const float* __restrict__ bo,
                                                         float* __restrict__ out, float* __restrict__ x_out,
                                                         float* __restrict__ y_out, int n) {
@@ -552,10 +544,12 @@ __global__ __launch_bounds__(256) void gated_out_kernel(const float* __restrict_
     float sx[8], sy[8], gz[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const float a = hx[(size_t)b * HD + lane + 64 * i], c = hy[(size_t)b * HD + lane + 64 * i];
+        const float a = gate[(size_t)b * HD + lane + 64 * i], c = val[(size_t)b * HD + lane + 64 * i];
         const float ga = sigmoidf_(a);
-        sx[i] = ga * a;
-        sy[i] = sigmoidf_(c) * c;
+        if (UNI) {
+            sx[i] = ga * a;
+            sy[i] = sigmoidf_(c) * c;
+        }
         gz[i] = ga * c;
     }
     for (int j = wave; j < n; j += 4) {
@@ -564,21 +558,25 @@ __global__ __launch_bounds__(256) void gated_out_kernel(const float* __restrict_
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float wv = w[lane + 64 * i];
-            px += wv * sx[i];
-            py += wv * sy[i];
-            pz += wv * gz[i];
+            if (UNI) {
+                px = fmaf(wv, sx[i], px);
+                py = fmaf(wv, sy[i], py);
+            }
+            pz = fmaf(wv, gz[i], pz);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            px += __shfl_xor(px, o);
-            py += __shfl_xor(py, o);
+            if (UNI) {
+                px += __shfl_xor(px, o);
+                py += __shfl_xor(py, o);
+            }
             pz += __shfl_xor(pz, o);
         }
         if (lane == 0) {
             const float bj = bo[j];
             out[(size_t)b * n + j] = pz + bj;
-            if (x_out) x_out[(size_t)b * n + j] = px + bj;
-            if (y_out) y_out[(size_t)b * n + j] = py + bj;
+            if (UNI && x_out) x_out[(size_t)b * n + j] = px + bj;
+            if (UNI && y_out) y_out[(size_t)b * n + j] = py + bj;
         }
     }
 }
@@ -587,7 +585,7 @@ int head_gated_fwd(const float* x, const float* y, const float* W1, const float*
                    hipStream_t st) {
     hipLaunchKernelGGL(gated_hidden_kernel, dim3(B, 2), dim3(256), 0, st, x, y, W1, b1, W2, b2, hx, hy);
     GDL_CHECK_LAUNCH("gated_hidden_kernel");
-    hipLaunchKernelGGL(gated_out_kernel, dim3(B), dim3(256), 0, st, hx, hy, Wo, bo, out, x_out, y_out, n);
+    hipLaunchKernelGGL(gated_out_kernel<true>, dim3(B), dim3(256), 0, st, hx, hy, Wo, bo, out, x_out, y_out, n);
     GDL_CHECK_LAUNCH("gated_out_kernel");
     return GDL_OK;
 }
@@ -604,9 +602,9 @@ __global__ __launch_bounds__(256) void gated_dh_kernel(const float* __restrict__
     for (int j = threadIdx.x; j < HD; j += 256) {
         float s = 0.f;
         if (g)
-            for (int c = 0; c < n; ++c) s += g[(size_t)b * n + c] * Wo[(size_t)c * HD + j];
+            for (int c = 0; c < n; ++c) s = fmaf(g[(size_t)b * n + c], Wo[(size_t)c * HD + j], s);
         const float hv = h[j], sg = sigmoidf_(hv);
-        dh[j] = s * sg * (1.f + hv * (1.f - sg));
+        dh[j] = s * sg * fmaf(hv, 1.f - sg, 1.f);
     }
 }
 // grid = (B, 2): dx[b][i] = sum_j dhx[b][j] W1[j][i]   (threads along i: coalesced rows of W1)
@@ -622,7 +620,7 @@ __global__ __launch_bounds__(256) void gated_dx_kernel(const float* __restrict__
     __syncthreads();
     for (int i = threadIdx.x; i < HD; i += 256) {
         float s = 0.f;
-        for (int j = 0; j < HD; ++j) s += dh[j] * W[(size_t)j * HD + i];
+        for (int j = 0; j < HD; ++j) s = fmaf(dh[j], W[(size_t)j * HD + i], s);
         dst[i] = s;
     }
 }
@@ -637,10 +635,10 @@ __global__ __launch_bounds__(256) void gated_dwo_kernel(const float* __restrict_
         for (int b = 0; b < B; ++b) {
             const float a = hx[(size_t)b * HD + j], v = hy[(size_t)b * HD + j];
             const float ga = sigmoidf_(a);
-            if (g_out) s += g_out[(size_t)b * n + c] * ga * v;
+            if (g_out) s = fmaf(v, g_out[(size_t)b * n + c] * ga, s);
             if (uni_in_dw) {
-                if (g_x_out) s += g_x_out[(size_t)b * n + c] * ga * a;
-                if (g_y_out) s += g_y_out[(size_t)b * n + c] * sigmoidf_(v) * v;
+                if (g_x_out) s = fmaf(a, g_x_out[(size_t)b * n + c] * ga, s);
+                if (g_y_out) s = fmaf(v, g_y_out[(size_t)b * n + c] * sigmoidf_(v), s);
             }
         }
         dWo[(size_t)c * HD + j] = s;
@@ -669,7 +667,7 @@ __global__ __launch_bounds__(256) void gated_dw1_kernel(const float* __restrict_
     float* db = which ? db2 : db1;
     for (int i = threadIdx.x; i < HD; i += 256) {
         float s = 0.f;
-        for (int b = 0; b < B; ++b) s += dh[(size_t)b * HD + j] * in[(size_t)b * HD + i];
+        for (int b = 0; b < B; ++b) s = fmaf(dh[(size_t)b * HD + j], in[(size_t)b * HD + i], s);
         dW[(size_t)j * HD + i] = s;
     }
     if (threadIdx.x == 0) {
@@ -706,41 +704,15 @@ int head_gated_bwd(const float* x, const float* y, const float* hx, const float*
 // ---------------------------------------------------------------- GatedFusion, trained jointly (fusion_modules.py:181-210)
 //   hx = fc_x(x), hy = fc_y(y);  x_gate: out = fc_out(sigmoid(hx) * hy),  else: out = fc_out(hx * sigmoid(hy))
 // One cross-entropy on `out` reaches all six tensors and both feature vectors (no detach anywhere).
-// grid = B: the fused logits alone; per class the same products, lane order and butterfly as gated_out_kernel's `out`
-// (x_gate = 1: bit-identical to the DGL head's `out`)
-__global__ __launch_bounds__(256) void gated_joint_out_kernel(const float* __restrict__ hx, const float* __restrict__ hy,
-                                                              const float* __restrict__ Wo, const float* __restrict__ bo,
-                                                              float* __restrict__ out, int x_gate, int n) {
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* gate = (x_gate ? hx : hy) + (size_t)b * HD;
-    const float* val = (x_gate ? hy : hx) + (size_t)b * HD;
-    float gz[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float a = gate[lane + 64 * i], c = val[lane + 64 * i];
-        const float ga = sigmoidf_(a);
-        gz[i] = ga * c;
-    }
-    for (int j = wave; j < n; j += 4) {
-        const float* w = Wo + (size_t)j * HD;
-        float pz = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float wv = w[lane + 64 * i];
-            pz += wv * gz[i];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pz += __shfl_xor(pz, o);
-        if (lane == 0) out[(size_t)b * n + j] = pz + bo[j];
-    }
-}
+// The fused logits are gated_out_kernel<false> on (gate, value): x_gate = 1 is bit-identical to the DGL head's `out`.
 int head_gated_joint_fwd(const float* x, const float* y, const float* W1, const float* b1, const float* W2, const float* b2,
                          const float* Wo, const float* bo, float* hx, float* hy, float* out, int x_gate, int B, int n,
                          hipStream_t st) {
     hipLaunchKernelGGL(gated_hidden_kernel, dim3(B, 2), dim3(256), 0, st, x, y, W1, b1, W2, b2, hx, hy);
     GDL_CHECK_LAUNCH("gated_hidden_kernel");
-    hipLaunchKernelGGL(gated_joint_out_kernel, dim3(B), dim3(256), 0, st, hx, hy, Wo, bo, out, x_gate, n);
-    GDL_CHECK_LAUNCH("gated_joint_out_kernel");
+    hipLaunchKernelGGL(gated_out_kernel<false>, dim3(B), dim3(256), 0, st, x_gate ? hx : hy, x_gate ? hy : hx, Wo, bo, out,
+                       (float*)nullptr, (float*)nullptr, n);
+    GDL_CHECK_LAUNCH("gated_out_kernel");
     return GDL_OK;
 }
 // grid = B, a thread per hidden unit j:  dm = sum_c g_out[b][c] Wo[c][j]  (classes in ascending order), s = sigmoid(gate[j]):
@@ -756,7 +728,7 @@ __global__ __launch_bounds__(256) void gated_joint_dh_kernel(const float* __rest
     float* dval = (x_gate ? dhy : dhx) + (size_t)b * HD;
     for (int j = threadIdx.x; j < HD; j += 256) {
         float dm = 0.f;
-        for (int c = 0; c < n; ++c) dm += g_out[(size_t)b * n + c] * Wo[(size_t)c * HD + j];
+        for (int c = 0; c < n; ++c) dm = fmaf(g_out[(size_t)b * n + c], Wo[(size_t)c * HD + j], dm);
         const float s = sigmoidf_(gate[j]);
         dval[j] = dm * s;
         dgate[j] = dm * val[j] * (s * (1.f - s));

@@ -2,7 +2,8 @@
 // walk helpers it is made of.  head_uni_dfeat_kernel (head.hip, the DGL step) IS this body; head_cls_ce_kernel (head_cls.hip,
 // the unimodal step) is this body with its two stores compiled in (STORE), plus the sample's loss term and the loss sum;
 // head_cls_fwd_kernel / head_cls_dfeat_kernel use the helpers; linprobe_ce_kernel (linprobe.hip, the linear probe's fit) is the
-// body's first part, head_ce_logits, on a row gathered from a feature bank.  Every sum has ONE order and ONE spelling (explicit fmaf: the bits do not depend on the contraction default):
+// body's first part, head_ce_logits, on a row gathered from a feature bank.  Every sum has ONE order and ONE spelling -- an explicit
+// fmaf chain, here and in the kernels of head.hip / head_film.hip whose orders these reproduce:
 //   a logit      : lane l of a wave adds W[j][l + 64 i] * f[l + 64 i] for i = 0 .. ND-1 (fmaf chain), xor butterfly 32 .. 1, + b[j]
 //   softmax / CE : softmax_ce_block's (head.hip) -- max (exact in any order), expf(l - max) summed in class order,
 //                  lse = max + logf(sum), dlogits = scale * (expf(l - lse) - onehot) / B

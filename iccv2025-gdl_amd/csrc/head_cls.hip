@@ -20,6 +20,7 @@
 #include "head_body.h"
 #include "ops.h"
 #include "prof.h"
+#include "ticket.h"
 
 namespace gdl {
 
@@ -104,13 +105,9 @@ int head_cls_bwd(const float* f, const float* W, const float* g_out, float* df, 
 // three stores the unimodal step needs -- out and dlogits (the body's STORE) and the sample's loss term.
 //
 // The mean over the samples = over the blocks.  df occupies waves 0 .. 7 only; wave 15, idle by then, publishes the sample's
-// term (lse - logit[label]) and draws a ticket; the block whose ticket is the last sums all B terms in ONE order (lane l takes
-// b = l, l + 64, ..., then the xor butterfly 32 .. 1), writes loss[0] and zeroes the counter for the next launch.  No
-// floating-point atomic; the result does not depend on which block comes last.
-// Visibility between the blocks (per-XCD L2s are not coherent): the term is an agent-scope (write-through) store of the one
-// lane that also draws the ticket, waited for before the ticket's agent-scope acq_rel add; the reader's loads are agent-scope
-// loads issued after its add has returned.  `part` / `cnt` belong to the launching stream (ce_slot below): launches of one
-// stream are ordered, so the counter is 0 at every kernel start.
+// term (lse - logit[label]) and draws a ticket (ticket.h: the protocol and its visibility argument); the block whose ticket is
+// the last sums all B terms in ONE order of this kernel's own (lane l takes b = l, l + 64, ..., then the xor butterfly
+// 32 .. 1), writes loss[0] and hands the counter back.  `part` / `cnt` belong to the launching stream (ce_slot below).
 __global__ __launch_bounds__(1024) void head_cls_ce_kernel(const float* __restrict__ f, const float* __restrict__ W,
                                                           const float* __restrict__ bias, const int64_t* __restrict__ labels,
                                                           float scale, float* __restrict__ out, float* __restrict__ loss,
@@ -123,18 +120,17 @@ __global__ __launch_bounds__(1024) void head_cls_ce_kernel(const float* __restri
         int last = 0;
         if (lane == 0) {
             st_agent(part + b, lab >= 0 ? s.lse - s.lg[lab] : __builtin_nanf(""));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(B - 1);
+            last = ticket_draw(cnt, B);
         }
         last = __shfl(last, 0);
         if (last) {
             float t = 0.f;
-            for (int k = lane; k < B; k += 64) t += __hip_atomic_load(part + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int k = lane; k < B; k += 64) t += ld_agent(part + k);
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
             if (lane == 0) {
                 loss[0] = t / (float)B;
-                __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ticket_hand_back(cnt);
             }
         }
     }

@@ -27,37 +27,43 @@ constexpr int FROWS = FD * FD;     // rows of fc.weight viewed as [FROWS][FD]
 constexpr int FILM_MAX_B = 512;
 static inline int film_bp(int B) { return (B + 31) / 32 * 32; }  // batch padded so that 2*Bp % 64 == 0, 3*Bp % 32 == 0
 
-// ---- V[2*Bp][512]: rows 0..B-1 = x, rows Bp..Bp+B-1 = y, padding rows zero
-__global__ void film_v_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ V, int B, int Bp) {
-    const int r = blockIdx.x;  // 0 .. 2*Bp-1
-    const int b = r < Bp ? r : r - Bp;
-    const float* src = b < B ? (r < Bp ? x : y) + (size_t)b * FD : nullptr;
+// ---- V: planes of ld rows, plane 0 = x, plane 1 = y (rows 0..B-1 of a plane, padding rows zero), from plane p0 on: the DGL
+// head's V[2*Bp][512] is (ld = Bp, p0 = 0, grid 2*Bp), the joint head's y rows alone (ld = Bj, p0 = 1, grid Bj)
+__global__ void film_v_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ V, int B, int ld,
+                              int p0) {
+    const int r = blockIdx.x;
+    const int b = r < ld ? r : r - ld;
+    const float* src = b < B ? ((r < ld ? p0 : 1) ? y : x) + (size_t)b * FD : nullptr;
     for (int i = threadIdx.x; i < FD; i += blockDim.x) V[(size_t)r * FD + i] = src ? src[i] : 0.f;
 }
 
-// ---- h[b][k] = bias[k] + sum_i left_b[i] * T[(k,i)][col(b)]     grid = (512 k, 3 forms, ceil(B / 64) sample groups):
-// 0 = x form, 1 = fused, 2 = y form
+// ---- h[b][k] = bias[k] + sum_i left_b[i] * T[(k,i)][col(b)]     grid = (512 k, forms, ceil(B / 64) sample groups):
+// form = form0 + blockIdx.y: 0 = x form, 1 = fused, 2 = y form.  T has ld columns, W_k x_b at b, W_k y_b at ycol + b: the DGL
+// head's three forms are (ld = 2*Bp, ycol = Bp, form0 = 0), the joint head's fused form alone (ld = Bj, ycol = 0, form0 = 1,
+// one form; hx, hy unused) -- the same four slices of i and the same order of the partial sums
 __global__ __launch_bounds__(256) void film_h_kernel(const float* __restrict__ T, const float* __restrict__ x,
                                                      const float* __restrict__ y, const float* __restrict__ bias,
                                                      float* __restrict__ hx, float* __restrict__ hf, float* __restrict__ hy,
-                                                     int B, int Bp) {
+                                                     int B, int ld, int ycol, int form0) {
     __shared__ float red[4][64];
-    const int k = blockIdx.x, form = blockIdx.y;
+    const int k = blockIdx.x, form = form0 + blockIdx.y;
     const float* left = form == 2 ? y : x;                 // x^T W_k x, x^T W_k y, y^T W_k y
-    const int coff = form == 0 ? 0 : Bp;                   // T columns: W_k x_b at b, W_k y_b at Bp + b
+    const int coff = form == 0 ? 0 : ycol;
     float* h = form == 0 ? hx : (form == 1 ? hf : hy);
     const int bl = threadIdx.x & 63, b = blockIdx.z * 64 + bl, part = threadIdx.x >> 6;  // 4 slices of i
     float s = 0.f;
     if (b < B) {
-        const float* Tk = T + (size_t)k * FD * (2 * Bp) + coff + b;
-        for (int i = part; i < FD; i += 4) s += left[(size_t)b * FD + i] * Tk[(size_t)i * (2 * Bp)];
+        const float* Tk = T + (size_t)k * FD * ld + coff + b;
+        for (int i = part; i < FD; i += 4) s = fmaf(Tk[(size_t)i * ld], left[(size_t)b * FD + i], s);
     }
     red[part][bl] = s;
     __syncthreads();
     if (part == 0 && b < B) h[(size_t)b * FD + k] = ((red[0][bl] + red[1][bl]) + red[2][bl]) + red[3][bl] + bias[k];
 }
 
-// ---- logits of the three hidden vectors: grid = B
+// ---- logits of the three hidden vectors: grid = B.  Without UNI (the joint head) the fused set alone, from hf (hx, hy unused):
+// the same products, lane order and butterfly
+template <bool UNI>
 __global__ __launch_bounds__(256) void film_out_kernel(const float* __restrict__ hx, const float* __restrict__ hf,
                                                        const float* __restrict__ hy, const float* __restrict__ Wo,
                                                        const float* __restrict__ bo, float* __restrict__ out,
@@ -66,9 +72,9 @@ __global__ __launch_bounds__(256) void film_out_kernel(const float* __restrict__
     float a[8], f[8], c[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        a[i] = hx[(size_t)b * FD + lane + 64 * i];
+        if (UNI) a[i] = hx[(size_t)b * FD + lane + 64 * i];
         f[i] = hf[(size_t)b * FD + lane + 64 * i];
-        c[i] = hy[(size_t)b * FD + lane + 64 * i];
+        if (UNI) c[i] = hy[(size_t)b * FD + lane + 64 * i];
     }
     for (int j = wave; j < n; j += 4) {
         const float* w = Wo + (size_t)j * FD;
@@ -76,20 +82,20 @@ __global__ __launch_bounds__(256) void film_out_kernel(const float* __restrict__
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float wv = w[lane + 64 * i];
-            px += wv * a[i];
-            pf += wv * f[i];
-            py += wv * c[i];
+            if (UNI) px = fmaf(wv, a[i], px);
+            pf = fmaf(wv, f[i], pf);
+            if (UNI) py = fmaf(wv, c[i], py);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            px += __shfl_xor(px, o);
+            if (UNI) px += __shfl_xor(px, o);
             pf += __shfl_xor(pf, o);
-            py += __shfl_xor(py, o);
+            if (UNI) py += __shfl_xor(py, o);
         }
         if (lane == 0) {
             out[(size_t)b * n + j] = pf + bo[j];
-            if (x_out) x_out[(size_t)b * n + j] = px + bo[j];
-            if (y_out) y_out[(size_t)b * n + j] = py + bo[j];
+            if (UNI && x_out) x_out[(size_t)b * n + j] = px + bo[j];
+            if (UNI && y_out) y_out[(size_t)b * n + j] = py + bo[j];
         }
     }
 }
@@ -103,7 +109,7 @@ __global__ __launch_bounds__(256) void film_dh_kernel(const float* __restrict__ 
     for (int k = threadIdx.x; k < FD; k += 256) {
         float s = 0.f;
         if (g)
-            for (int c = 0; c < n; ++c) s += g[(size_t)b * n + c] * Wo[(size_t)c * FD + k];
+            for (int c = 0; c < n; ++c) s = fmaf(g[(size_t)b * n + c], Wo[(size_t)c * FD + k], s);
         dh[((size_t)form * B + b) * FD + k] = s;
     }
 }
@@ -117,10 +123,10 @@ __global__ __launch_bounds__(256) void film_dwo_kernel(const float* __restrict__
     for (int k = threadIdx.x; k < FD; k += 256) {
         float s = 0.f;
         for (int b = 0; b < B; ++b) {
-            if (g_out) s += g_out[(size_t)b * n + c] * hf[(size_t)b * FD + k];
+            if (g_out) s = fmaf(g_out[(size_t)b * n + c], hf[(size_t)b * FD + k], s);
             if (uni) {
-                if (g_x_out) s += g_x_out[(size_t)b * n + c] * hx[(size_t)b * FD + k];
-                if (g_y_out) s += g_y_out[(size_t)b * n + c] * hy[(size_t)b * FD + k];
+                if (g_x_out) s = fmaf(g_x_out[(size_t)b * n + c], hx[(size_t)b * FD + k], s);
+                if (g_y_out) s = fmaf(g_y_out[(size_t)b * n + c], hy[(size_t)b * FD + k], s);
             }
         }
         dWo[(size_t)c * FD + k] = s;
@@ -138,11 +144,13 @@ __global__ __launch_bounds__(256) void film_dwo_kernel(const float* __restrict__
     }
 }
 
-// ---- U[(k,j)][col]: col b -> dh_x[b][k] * x_b[j], col Bp+b -> dh_y[b][k] * y_b[j], padding columns zero.
-// one thread per (row, 4 columns)
+// ---- U[(k,j)][col], padding columns zero; one thread per (row, 4 columns).  XY (the DGL head): 2*Bp columns, col b ->
+// dh_x[b][k] * x_b[j], col Bp+b -> dh_y[b][k] * y_b[j], the planes 0 / 2 of dh.  Without XY (the joint head): the one plane of Bp
+// columns (the caller's Bj), col b -> dh[b][k] * x_b[j] with dh the fused plane; y unused.
+template <bool XY>
 __global__ __launch_bounds__(256) void film_u_kernel(const float* __restrict__ dh, const float* __restrict__ x,
                                                      const float* __restrict__ y, float* __restrict__ U, int B, int Bp) {
-    const int cols = 2 * Bp, c4 = cols / 4;
+    const int cols = XY ? 2 * Bp : Bp, c4 = cols / 4;
     const size_t total = (size_t)FROWS * c4;
     for (size_t t = blockIdx.x * (size_t)256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const int q = (int)(t % c4);
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(256) void film_u_kernel(const float* __restrict__ d
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int col = q * 4 + e, isy = col >= Bp, b = isy ? col - Bp : col;
+            const int col = q * 4 + e, isy = XY && col >= Bp, b = isy ? col - Bp : col;
             v[e] = b < B ? dh[((size_t)(isy ? 2 : 0) * B + b) * FD + k] * (isy ? y : x)[(size_t)b * FD + j] : 0.f;
         }
         *(float4*)(U + row * cols + q * 4) = make_float4(v[0], v[1], v[2], v[3]);
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(256) void film_dxy_kernel(const float* __restrict__
     float* dst = (isy ? dy : dx) + (size_t)b * FD;
     for (int i = threadIdx.x; i < FD; i += 256) {
         float s = out2[(size_t)col * FD + i];
-        for (int k = 0; k < FD; ++k) s += dhb[k] * T[((size_t)k * FD + i) * (2 * Bp) + col];
+        for (int k = 0; k < FD; ++k) s = fmaf(dhb[k], T[((size_t)k * FD + i) * (2 * Bp) + col], s);
         dst[i] = s;
     }
 }
@@ -256,16 +264,16 @@ int head_film_fwd(const float* x, const float* y, const float* Wfc, const float*
     }
     const int Bp = film_bp(B);
     float *hx = hidden, *hf = hidden + (size_t)B * FD, *hy = hidden + (size_t)2 * B * FD;
-    hipLaunchKernelGGL(film_v_kernel, dim3(2 * Bp), dim3(256), 0, st, x, y, w.V, B, Bp);
+    hipLaunchKernelGGL(film_v_kernel, dim3(2 * Bp), dim3(256), 0, st, x, y, w.V, B, Bp, 0);
     GDL_CHECK_LAUNCH("film_v_kernel");
     int rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, FD, 2 * Bp, 1, 1, 1, 0, (GatherEntry*)w.tab_a, st);
     if (rc) return rc;
     // T[(k,i)][col] = sum_j A[(k,i)][j] V[col][j]
     rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, 1, FROWS, 1, FD, 2 * Bp, 1, 1, 1, 0, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(film_h_kernel, dim3(FD, 3, (B + 63) / 64), dim3(256), 0, st, w.T, x, y, bfc, hx, hf, hy, B, Bp);
+    hipLaunchKernelGGL(film_h_kernel, dim3(FD, 3, (B + 63) / 64), dim3(256), 0, st, w.T, x, y, bfc, hx, hf, hy, B, 2 * Bp, Bp, 0);
     GDL_CHECK_LAUNCH("film_h_kernel");
-    hipLaunchKernelGGL(film_out_kernel, dim3(B), dim3(256), 0, st, hx, hf, hy, Wo, bo, out, x_out, y_out, n);
+    hipLaunchKernelGGL(film_out_kernel<true>, dim3(B), dim3(256), 0, st, hx, hf, hy, Wo, bo, out, x_out, y_out, n);
     GDL_CHECK_LAUNCH("film_out_kernel");
     return GDL_OK;
 }
@@ -292,7 +300,7 @@ int head_film_bwd(const float* x, const float* y, const float* Wfc, const float*
     }
     int rc;
     if (dx && dy) {
-        hipLaunchKernelGGL(film_u_kernel, dim3(4096), dim3(256), 0, st, w.dh, x, y, w.U, B, Bp);
+        hipLaunchKernelGGL(film_u_kernel<true>, dim3(4096), dim3(256), 0, st, w.dh, x, y, w.U, B, Bp);
         GDL_CHECK_LAUNCH("film_u_kernel");
         // out2[col][i] = sum_(k,j) U[(k,j)][col] A[(k,j)][i]
         rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, 1, FROWS, 1, FD, 2 * Bp, 1, 1, 1, 0, FD, w.wg, w.wg_bytes, st);
@@ -329,64 +337,6 @@ int head_film_bwd(const float* x, const float* y, const float* Wfc, const float*
 //      partials of the dy contraction (at most 27 MB of its >= 100 MB)
 static inline int film_bj(int B) { return (B + 63) / 64 * 64; }
 
-__global__ void film_vy_kernel(const float* __restrict__ y, float* __restrict__ V, int B) {
-    const int r = blockIdx.x;  // 0 .. Bj-1
-    for (int i = threadIdx.x; i < FD; i += blockDim.x) V[(size_t)r * FD + i] = r < B ? y[(size_t)r * FD + i] : 0.f;
-}
-// h_f[b][k] = bias[k] + sum_i x_b[i] T[(k,i)][b]     grid = (512 k, ceil(B / 64)); film_h_kernel's fused form: the same four
-// slices of i, the same order of the partial sums
-__global__ __launch_bounds__(256) void film_hf_kernel(const float* __restrict__ T, const float* __restrict__ x,
-                                                      const float* __restrict__ bias, float* __restrict__ hf, int B, int ld) {
-    __shared__ float red[4][64];
-    const int k = blockIdx.x;
-    const int bl = threadIdx.x & 63, b = blockIdx.y * 64 + bl, part = threadIdx.x >> 6;
-    float s = 0.f;
-    if (b < B) {
-        const float* Tk = T + (size_t)k * FD * ld + b;
-        for (int i = part; i < FD; i += 4) s += x[(size_t)b * FD + i] * Tk[(size_t)i * ld];
-    }
-    red[part][bl] = s;
-    __syncthreads();
-    if (part == 0 && b < B) hf[(size_t)b * FD + k] = ((red[0][bl] + red[1][bl]) + red[2][bl]) + red[3][bl] + bias[k];
-}
-// out[b][j] = bo[j] + sum_k Wo[j][k] h_f[b][k]      grid = B; film_out_kernel's fused logit set
-__global__ __launch_bounds__(256) void film_joint_out_kernel(const float* __restrict__ hf, const float* __restrict__ Wo,
-                                                             const float* __restrict__ bo, float* __restrict__ out, int n) {
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float f[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = hf[(size_t)b * FD + lane + 64 * i];
-    for (int j = wave; j < n; j += 4) {
-        const float* w = Wo + (size_t)j * FD;
-        float pf = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float wv = w[lane + 64 * i];
-            pf += wv * f[i];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pf += __shfl_xor(pf, o);
-        if (lane == 0) out[(size_t)b * n + j] = pf + bo[j];
-    }
-}
-// U[(k,i)][b] = dh_f[b][k] * x_b[i], padding columns zero.  One thread per (row, 4 columns)
-__global__ __launch_bounds__(256) void film_uj_kernel(const float* __restrict__ dhf, const float* __restrict__ x,
-                                                      float* __restrict__ U, int B, int ld) {
-    const int c4 = ld / 4;
-    const size_t total = (size_t)FROWS * c4;
-    for (size_t t = blockIdx.x * (size_t)256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
-        const int q = (int)(t % c4);
-        const size_t row = t / c4;
-        const int k = (int)(row / FD), i = (int)(row % FD);
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int b = q * 4 + e;
-            v[e] = b < B ? dhf[(size_t)b * FD + k] * x[(size_t)b * FD + i] : 0.f;
-        }
-        *(float4*)(U + row * ld + q * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
 // dx[b][i] = sum_k dh_f[b][k] T[(k,i)][b]  (T is still in the workspace: no GEMM);  dy[b][i] = out2[b][i]
 // grid = (512 i, ceil(B / 64)): a lane per sample (coalesced rows of T), four slices of k summed in a fixed order
 __global__ __launch_bounds__(256) void film_joint_dxy_kernel(const float* __restrict__ T, const float* __restrict__ dhf,
@@ -398,7 +348,7 @@ __global__ __launch_bounds__(256) void film_joint_dxy_kernel(const float* __rest
     float s = 0.f;
     if (b < B) {
         const float* Ti = T + (size_t)i * ld + b;
-        for (int k = part; k < FD; k += 4) s += dhf[(size_t)b * FD + k] * Ti[(size_t)k * FD * ld];
+        for (int k = part; k < FD; k += 4) s = fmaf(dhf[(size_t)b * FD + k], Ti[(size_t)k * FD * ld], s);
     }
     red[part][bl] = s;
     __syncthreads();
@@ -418,17 +368,19 @@ int head_film_joint_fwd(const float* x, const float* y, const float* Wfc, const 
         return GDL_ERR_WORKSPACE;
     }
     const int Bj = film_bj(B);  // <= 2 * Bp: V, T, U and out2 of the DGL layout hold the Bj-column forms
-    hipLaunchKernelGGL(film_vy_kernel, dim3(Bj), dim3(256), 0, st, y, w.V, B);
-    GDL_CHECK_LAUNCH("film_vy_kernel");
+    hipLaunchKernelGGL(film_v_kernel, dim3(Bj), dim3(256), 0, st, (const float*)nullptr, y, w.V, B, Bj, 1);
+    GDL_CHECK_LAUNCH("film_v_kernel");
     int rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, (GatherEntry*)w.tab_a, st);
     if (rc) return rc;
     // T[(k,i)][b] = sum_j A[(k,i)][j] y_b[j]
     rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(film_hf_kernel, dim3(FD, (B + 63) / 64), dim3(256), 0, st, w.T, x, bfc, hidden, B, Bj);
-    GDL_CHECK_LAUNCH("film_hf_kernel");
-    hipLaunchKernelGGL(film_joint_out_kernel, dim3(B), dim3(256), 0, st, hidden, Wo, bo, out, n);
-    GDL_CHECK_LAUNCH("film_joint_out_kernel");
+    hipLaunchKernelGGL(film_h_kernel, dim3(FD, 1, (B + 63) / 64), dim3(256), 0, st, w.T, x, y, bfc, (float*)nullptr, hidden,
+                       (float*)nullptr, B, Bj, 0, 1);
+    GDL_CHECK_LAUNCH("film_h_kernel");
+    hipLaunchKernelGGL(film_out_kernel<false>, dim3(B), dim3(256), 0, st, (const float*)nullptr, hidden, (const float*)nullptr, Wo,
+                       bo, out, (float*)nullptr, (float*)nullptr, n);
+    GDL_CHECK_LAUNCH("film_out_kernel");
     return GDL_OK;
 }
 
@@ -454,8 +406,8 @@ int head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const 
     }
     int rc;
     if (dx && dy) {
-        hipLaunchKernelGGL(film_uj_kernel, dim3(4096), dim3(256), 0, st, dhf, x, w.U, B, Bj);
-        GDL_CHECK_LAUNCH("film_uj_kernel");
+        hipLaunchKernelGGL(film_u_kernel<false>, dim3(4096), dim3(256), 0, st, dhf, x, (const float*)nullptr, w.U, B, Bj);
+        GDL_CHECK_LAUNCH("film_u_kernel");
         // out2[b][j] = sum_(k,i) U[(k,i)][b] A[(k,i)][j]; the split partials go to the (not yet written) P piece
         rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, FD, w.P, (size_t)FROWS * 3 * Bp * 4, st);
         if (rc) return rc;

@@ -12,12 +12,14 @@
 //
 // Every sum has the order and the spelling of head_body.h (= of the three launches): the two 512-dots of a class are taken once
 // and serve all three logit sets (out = pa + pv + bias); softmax as in head_ce_body, three sets side by side (their serial
-// exp-sums on three different waves); g_a + g_f added before the walk; classes ascending in the walk.  The logits, the logit
+// exp-sums on three different waves) -- a text of its own: on head_ce_logits made a template over the number of sets this kernel
+// needs 2 KiB more LDS and measures 0.1 - 0.2 us slower at 64 x 309 (docs/measurement_log.md), so both are kept; g_a + g_f added before the walk; classes ascending in the walk.  The logits, the logit
 // gradients and dfa / dfv carry the bits of the three-launch path.
 #include "common.h"
 #include "head_body.h"
 #include "ops.h"
 #include "prof.h"
+#include "ticket.h"
 
 namespace gdl {
 
@@ -33,12 +35,9 @@ struct alignas(16) MtlLds {
     float mx[3], lse[3];
 };
 
-// grid = B, a sample per 1024-thread block.  The sample's three loss terms go the way head_cls_ce_kernel's one term goes: wave
-// 15 publishes them (agent-scope stores of the lane that then draws the ticket) and the block that draws the last ticket adds
-// the B terms of each loss in ONE order, writes losses[0..2] and hands the counter back at zero.  No floating-point atomic; the
-// sums do not depend on which block comes last.  The order is softmax_ce_block's (head.hip): 256 partial sums p[b & 255] taking
-// b, b + 256, ... in turn, then the tree p[i] += p[i + o], o = 128 .. 1 -- lane l holds p[l], p[l + 64], p[l + 128], p[l + 192],
-// folds them as the tree's first two levels do, and the xor butterfly 32 .. 1 is the rest of the tree.
+// grid = B, a sample per 1024-thread block.  The sample's three loss terms go the way head_cls_ce_kernel's one term goes
+// (ticket.h): wave 15 publishes them and draws the ticket, and the block that draws the last one adds the B terms of each loss
+// in ticket_fold256's order (= softmax_ce_block's), writes losses[0..2] and hands the counter back at zero.
 __global__ __launch_bounds__(1024) void head_mtl_ce_kernel(const float* __restrict__ fa, const float* __restrict__ fv,
                                                           const float* __restrict__ Wa, const float* __restrict__ Wv, int ldw,
                                                           const float* __restrict__ ba, const float* __restrict__ bv, int sum_bias,
@@ -127,25 +126,16 @@ __global__ __launch_bounds__(1024) void head_mtl_ce_kernel(const float* __restri
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) st_agent(part + (size_t)k * B + b, lab >= 0 ? s.lse[k] - s.lg[k][lab] : __builtin_nanf(""));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(B - 1);
+            last = ticket_draw(cnt, B);
         }
         last = __shfl(last, 0);
         if (last) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                float a[4] = {0.f, 0.f, 0.f, 0.f};
-                for (int i0 = lane; i0 < B; i0 += 256)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (i0 + 64 * q < B)
-                            a[q] += __hip_atomic_load(part + (size_t)k * B + i0 + 64 * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                float t = (a[0] + a[2]) + (a[1] + a[3]);
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+                const float t = ticket_fold256(part + (size_t)k * B, B, lane);
                 if (lane == 0) losses[k] = t / (float)B;
             }
-            if (lane == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) ticket_hand_back(cnt);
         }
     }
 }

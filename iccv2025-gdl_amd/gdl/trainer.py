@@ -744,11 +744,7 @@ class DGLTrainer(ArenaTrainer):
                  and (self.dv == 512 or (self.head == "concat" and self.dv in (768, 1024))))
         red = self.reducer
         if early:
-            pv = self.pviews
-            if self.head == "concat":  # fc_out [n][512 + dv] + one bias
-                wa, wv, ldw, ba, bv = L.ptr(pv[0]), pv[0].data_ptr() + 512 * 4, 512 + self.dv, L.ptr(pv[1]), L.ptr(pv[1])
-            else:  # fc_x, fc_y [n][512] with their biases
-                wa, wv, ldw, ba, bv = L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3])
+            wa, wv, ldw, ba, bv = self._uni_operands(self.dv)
             with torch.cuda.stream(self.s_v):
                 self.eng_v.forward(image, True, feat_out=self.fv)
                 self._diversity(self.eng_v, 1)
@@ -822,11 +818,9 @@ class DGLTrainer(ArenaTrainer):
         if self._mod_now:
             # OGM's unimodal scores from the pooled features and the head's current parameters (main.py:286-295), behind the
             # head forward on its stream (= the audio chain, the shorter one): the visual backward is not kept waiting
-            pv = self.pviews
-            if self.head == "concat":  # out_a = a W[:, :512]^T + b / 2, out_v = v W[:, 512:]^T + b / 2
-                wa, wv, ldw, ba, bv, bs = L.ptr(pv[0]), pv[0].data_ptr() + 512 * 4, 1024, L.ptr(pv[1]), L.ptr(pv[1]), 0.5
-            else:  # out_a = fc_x(a), out_v = fc_y(v)
-                wa, wv, ldw, ba, bv, bs = L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3]), 1.0
+            # concat: out_a = a W[:, :512]^T + b / 2, out_v = v W[:, 512:]^T + b / 2; sum: out_a = fc_x(a), out_v = fc_y(v)
+            wa, wv, ldw, ba, bv = self._uni_operands(512)
+            bs = 0.5 if self.head == "concat" else 1.0
             L.call("gdl_head_uni_scores", L.ptr(self.fa), L.ptr(self.fv), wa, wv, ldw, ba, bv, bs, L.ptr(label),
                    L.ptr(self.mod_prob), L.ptr(self.mod_scores), B, n, L.ptr(self.score_ws), self.score_ws.numel(), st)
         if not dgl and red is None:
@@ -836,6 +830,13 @@ class DGLTrainer(ArenaTrainer):
             with torch.cuda.stream(self.s_v):
                 red.launch("visual_rest")
         self._finish_step(main, st)
+
+    def _uni_operands(self, dv):
+        """(wa, wv, ldw, ba, bv): the two modalities' linear maps inside a concat or sum head, for a visual width of dv."""
+        pv = self.pviews
+        if self.head == "concat":  # fc_out [n][512 + dv] + one bias: the audio columns first
+            return L.ptr(pv[0]), pv[0].data_ptr() + 512 * 4, 512 + dv, L.ptr(pv[1]), L.ptr(pv[1])
+        return L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3])  # fc_x, fc_y [n][512] with their biases
 
     def _encoders_backward(self):
         """Both encoders' backward from self.dfa / self.dfv, the visual one (the critical path) enqueued first.  Data parallel:
@@ -867,12 +868,10 @@ class DGLTrainer(ArenaTrainer):
         """What stands between the forwards and the backward chains when the fused loss reaches the encoders (concat / sum head):
         the three logit sets, the three losses, their logit gradients and dfa / dfv -- gdl_head_mtl_ce, ONE launch; beyond its 512
         classes (or with the tuning aid GDL_MTL_FUSED=0) the three launches it replaces, bit for bit."""
-        pv, B, n = self.pviews, self.B, self.n_classes
+        B, n = self.B, self.n_classes
         if self.mtl_fused and n <= 512:
-            if self.head == "concat":  # fc_out [n][1024] + one bias
-                wa, wv, ldw, ba, bv, sb = L.ptr(pv[0]), pv[0].data_ptr() + 512 * 4, 1024, L.ptr(pv[1]), L.ptr(pv[1]), 0
-            else:  # fc_x, fc_y [n][512] with their biases
-                wa, wv, ldw, ba, bv, sb = L.ptr(pv[0]), L.ptr(pv[2]), 512, L.ptr(pv[1]), L.ptr(pv[3]), 1
+            wa, wv, ldw, ba, bv = self._uni_operands(512)
+            sb = 0 if self.head == "concat" else 1  # `out` carries one bias / bx + by
             L.call("gdl_head_mtl_ce", L.ptr(self.fa), L.ptr(self.fv), wa, wv, ldw, ba, bv, sb, L.ptr(label), self.alpha, 1,
                    L.ptr(self.out), L.ptr(self.out_a), L.ptr(self.out_v), self.losses.data_ptr(), L.ptr(self.g_f), L.ptr(self.g_a),
                    L.ptr(self.g_v), L.ptr(self.dfa), L.ptr(self.dfv), B, n, L.ptr(self.mtl_ws), self.mtl_ws.numel(), st)

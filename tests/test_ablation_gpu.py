@@ -100,12 +100,16 @@ def _ws(B):
     return torch.zeros(L.load().gdl_head_mtl_ce_workspace_bytes(B), dtype=torch.uint8, device=DEV)
 
 
-@pytest.mark.parametrize("n", [1, 6, 34, 309, 512])
-@pytest.mark.parametrize("B", [1, 5, 16])
+# B = 65 and 257: the loss fold's second lane stride (lane l adds b = l and l + 64) and its second lap (b and b + 256)
+MTL_SIZES = [(B, n) for B in (1, 5, 16) for n in (1, 6, 34, 309, 512)] + [(65, 6), (257, 6), (257, 34)]
+
+
+@pytest.mark.parametrize("B,n", MTL_SIZES)
 @pytest.mark.parametrize("kind", ["concat", "sum"])
 def test_head_mtl_ce(kind, B, n):
     """gdl_head_mtl_ce at one class, fewer classes than waves, a count that is no multiple of the 32-class round over the 16
-    waves, the largest dataset and the LDS limit; one sample, an odd batch, 16.  Per value of fused_reaches: the logits, the logit
+    waves, the largest dataset and the LDS limit; one sample, an odd batch, 16, and batches that reach the second lane stride and
+    the second lap of the loss fold.  Per value of fused_reaches: the logits, the logit
     gradients and dfa / dfv carry the bits of the three-launch path; all of them agree with float64 to rtol 1e-4 / atol 1e-6; each
     loss is within 2 (B - 1) 2^-24 relative of gdl_softmax_ce3's (two float32 summation orders of B non-negative terms); two
     runs on one workspace are bit-equal (the ticket counter comes back at zero)."""

@@ -31,6 +31,8 @@ RTOL = 1e-4
 COMBOS = {"f32-nhwc": (L.GDL_F32, L.GDL_LAYOUT_NHWC), "bf16-nhwc": (L.GDL_BF16, L.GDL_LAYOUT_NHWC),
           "f32-nchw": (L.GDL_F32, L.GDL_LAYOUT_NCHW)}
 OP_CASES = [(k, s) for k in ("relu", "shift32") for s in dr.SHAPES] + [("same", dr.SAME_SHAPE)]
+# image counts that reach the mean fold's second lane stride (65) and its second lap (257), at the smallest P whose d varies
+OP_CASES += [("relu", (65, 2, 1)), ("relu", (257, 2, 1))]
 WORST = {}
 _REF = {}
 

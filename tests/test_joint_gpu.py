@@ -177,7 +177,7 @@ def _film_params(n=6):
 @pytest.mark.parametrize("B", [5, 33, 65])
 def test_joint_film_float64(B):
     """The FiLM joint head against float64 (torch, on the device) at B = 5 (one padded column block), 33 (batch padding to 32
-    for the weight gradient, 64 for T) and 65 (a second 64-sample group in film_hf_kernel / film_joint_dxy_kernel)."""
+    for the weight gradient, 64 for T) and 65 (a second 64-sample group in film_h_kernel / film_joint_dxy_kernel)."""
     n = 6
     P = _film_params(n)
     gen = torch.Generator(device=DEV).manual_seed(B)

@@ -83,20 +83,27 @@ def _scores(layout, fa, fv, P, label, B, n):
         args = (L.ptr(P[0]), P[0].data_ptr() + 512 * 4, 1024, L.ptr(P[1]), L.ptr(P[1]), 0.5)
     else:
         args = (L.ptr(P[0]), L.ptr(P[2]), 512, L.ptr(P[1]), L.ptr(P[3]), 1.0)
-    for _ in range(2):  # twice on one workspace: the ticket counter comes back at zero
+    first = None
+    for _ in range(2):  # twice on one workspace: the ticket counter comes back at zero, and the second run repeats the bits
         L.call("gdl_head_uni_scores", L.ptr(fa), L.ptr(fv), *args, L.ptr(label), L.ptr(prob), L.ptr(scores), B, n, L.ptr(ws), nb,
                L.cur_stream())
+        if first is None:
+            first = (prob.clone(), scores.clone())
+            prob.fill_(float("nan")), scores.fill_(float("nan"))
     torch.cuda.synchronize()
     assert not ws.any()
+    for a, c in zip(first, (prob, scores)):
+        assert torch.equal(a.view(torch.int32), c.view(torch.int32))
     return prob, scores
 
 
-@pytest.mark.parametrize("B,n", [(5, 6), (33, 34), (3, 309)])
+@pytest.mark.parametrize("B,n", [(5, 6), (33, 34), (3, 309), (65, 6), (257, 6), (257, 34)])
 @pytest.mark.parametrize("layout", ["concat", "sum"])
 def test_score_kernel(layout, B, n):
     """gdl_head_uni_scores against NumPy float64 (rtol 1e-4: a 512-term fp32 dot through exp) for both weight layouts, with the
     inputs rebuilt so that each side leads once, and the coefficients the finalise kernel derives from the scores within
-    1e-6 + 1e-4 |want| (1 - tanh cancels near 0).  309 classes: more than a wavefront is wide; the odd B: row tails."""
+    1e-6 + 1e-4 |want| (1 - tanh cancels near 0).  309 classes: more than a wavefront is wide; the odd B: row tails; B = 65 and 257: more blocks than a
+    wavefront has lanes and than one 256-sample lap, each run twice with bit-equal results."""
     r = np.random.default_rng([5, B, n, layout == "sum"])
     shapes = ((n, 1024), (n,)) if layout == "concat" else ((n, 512), (n,), (n, 512), (n,))
     Pn = [(r.standard_normal(s) * (0.05 if len(s) == 2 else 0.1)).astype(np.float32) for s in shapes]

@@ -18,7 +18,7 @@ from gdl import _lib as L  # noqa: E402
 from gpu_util import DEV, dev  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SIZES = [(5, 6), (33, 34), (4, 309), (64, 400)]  # (B, n): see test_head_float64
+SIZES = [(5, 6), (33, 34), (4, 309), (64, 400), (65, 6), (257, 6), (257, 34)]  # (B, n): see test_head_float64
 NAN = float("nan")
 
 
@@ -79,7 +79,8 @@ def _check64_param(got, ref, key):
 def test_head_float64(B, n):
     """gdl_head_cls_fwd / _bwd against a float64 restatement at a batch that is a multiple of nothing (5, 6), one past a
     32-sample group (33, 34), class counts that are no multiple of 8 and beyond any per-wave round (4, 309) and the largest head
-    the datasets have (64, 400).  Each optional output passed as NULL once: the others keep their bits, its buffer stays NaN."""
+    the datasets have (64, 400); (65, 6), (257, 6) and (257, 34) take gdl_head_cls_ce's loss sum to its second lane stride (lane l
+    adds samples l and l + 64) and past 256 blocks.  Each optional output passed as NULL once: the others keep their bits, its buffer stays NaN."""
     f, W, b, go, _ = _head_case(B, n)
     out = _cls_fwd(f, W, b)
     df, dW, db = _cls_bwd(f, W, go)
