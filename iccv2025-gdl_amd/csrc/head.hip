@@ -771,8 +771,9 @@ __global__ __launch_bounds__(256) void eval_count_kernel(const float* __restrict
                                                          unsigned long long* acc_a, unsigned long long* acc_v) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B) return;
-    const int lab = (int)labels[i];
-    if (lab < 0 || lab >= n) return;  // (the reference would raise an IndexError)
+    const long lab64 = (long)labels[i];  // range-checked at 64 bits, as softmax_ce_block does: 2^32 + k is no class k
+    if (lab64 < 0 || lab64 >= n) return;  // (the reference would raise an IndexError)
+    const int lab = (int)lab64;
     const float* rows[3] = {out + (size_t)i * n, out_a ? out_a + (size_t)i * n : nullptr, out_v ? out_v + (size_t)i * n : nullptr};
     unsigned long long* cnt[3] = {acc, acc_a, acc_v};
     atomicAdd(&num[lab], 1ULL);

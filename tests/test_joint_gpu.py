@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import head_ref as R
 from oracle import fixtures as fx
 
 pytestmark = pytest.mark.gpu
@@ -58,8 +59,8 @@ def _joint_fwd(kind, P, x, y, x_gate=True):
     return out, (hidden, ws)
 
 
-def _joint_bwd(kind, P, x, y, saved, go, x_gate=True):
-    """(dx, dy, [parameter gradients in named_parameters() order]) from g_out."""
+def _joint_bwd(kind, P, x, y, saved, go, x_gate=True, keep=None):
+    """(dx, dy, [parameter gradients in named_parameters() order]) from g_out; keep (a dict): the gated head's ws goes there."""
     B, n = x.shape[0], P[-1].shape[0]
     dx, dy = torch.full_like(x, float("nan")), torch.full_like(y, float("nan"))
     G = [torch.full_like(p, float("nan")) for p in P]
@@ -72,6 +73,8 @@ def _joint_bwd(kind, P, x, y, saved, go, x_gate=True):
         ws = torch.empty(2 * B * 512, device=DEV)
         L.call("gdl_head_gated_joint_bwd", L.ptr(x), L.ptr(y), L.ptr(hx), L.ptr(hy), L.ptr(P[0]), L.ptr(P[2]), L.ptr(P[4]), L.ptr(go),
                int(x_gate), L.ptr(dx), L.ptr(dy), *(L.ptr(g) for g in G), L.ptr(ws), B, n, s)
+        if keep is not None:
+            keep["ws"] = ws
     else:
         hidden, ws = saved
         L.call("gdl_head_film_joint_bwd", L.ptr(x), L.ptr(y), L.ptr(P[0]), L.ptr(P[2]), L.ptr(hidden), L.ptr(go), L.ptr(dx), L.ptr(dy),
@@ -128,38 +131,82 @@ def _randn(gen, *shape):
     return torch.randn(*shape, generator=gen, device=DEV)
 
 
+def _bound64(got, ref, key):
+    """within the derived bound of tests/head_ref.py, element by element"""
+    ex = R.excess(got.cpu().numpy(), ref[0], ref[1])
+    print(key, "excess", ex)
+    assert ex <= 1.0, (key, "is", ex, "bounds from the float64 value")
+
+
 @pytest.mark.parametrize("B,n", [(5, 6), (33, 34)])
 @pytest.mark.parametrize("kind,x_gate", [("sum", True), ("gated", True), ("gated", False)])
 def test_joint_head_float64(kind, x_gate, B, n):
-    """The sum and gated joint heads against a float64 restatement at a batch that is no multiple of anything and one beyond a
-    32-sample group, with more classes than a block has waves."""
+    """The sum and gated joint heads against the float64 restatements of tests/head_ref.py, every element within the bound derived
+    there, at a batch that is no multiple of anything and one beyond a 32-sample group, with more classes than a block has waves.
+    Sum: the whole forward and backward (each output is one sum deep).  Gated: stage by stage, each stage restated from the
+    device's own output of the stage before (hx / hy, the halves of ws).  The end-to-end comparison this test made before (1e-3 /
+    1e-3 on logits and feature gradients, 1e-3 of the largest element + 1e-6 on parameter gradients) stays beside them."""
     gen = torch.Generator(device=DEV).manual_seed(100 * B + n)
     P = [_randn(gen, *sh) * (0.05 if len(sh) == 2 else 0.1) for sh in _head_shapes(kind, n)]
     x, y = _randn(gen, B, 512).clamp_min(0), _randn(gen, B, 512).clamp_min(0)
     go = _randn(gen, B, n) / B
     out, saved = _joint_fwd(kind, P, x, y, x_gate)
-    dx, dy, G = _joint_bwd(kind, P, x, y, saved, go, x_gate)
+    keep = {}
+    dx, dy, G = _joint_bwd(kind, P, x, y, saved, go, x_gate, keep)
+    Pn = [p.cpu().numpy() for p in P]
+    xn, yn, gn = x.cpu().numpy(), y.cpu().numpy(), go.cpu().numpy()
+    if kind == "sum":
+        f = R.lin_fwd(R.F64, "sum", xn, yn, Pn[0], Pn[1], Pn[2], Pn[3])
+        b = R.lin_bwd(R.F64, "sum", xn, yn, Pn[0], Pn[2], None, None, gn, 1, 0)
+        _bound64(out, f["out"], "out")
+        _bound64(dx, b["dx"], "dx")
+        _bound64(dy, b["dy"], "dy")
+        for k, t, r in zip(HEAD_NAMES[kind], G, ("dWx", "dbx", "dWy", "dby")):
+            _bound64(t, b[r], k)
+        D = [p.double() for p in P]
+        xd, yd, gd = x.double(), y.double(), go.double()
+        _check64(out, xd @ D[0].T + D[1] + yd @ D[2].T + D[3], "out")
+        _check64(dx, gd @ D[0], "dx")
+        _check64(dy, gd @ D[2], "dy")
+        for k, t, r in zip(HEAD_NAMES[kind], G, [gd.T @ xd, gd.sum(0), gd.T @ yd, gd.sum(0)]):
+            _check64_param(t, r, k)
+        return
+    hxn, hyn = saved[0].cpu().numpy(), saved[1].cpu().numpy()
+    h = R.gated_hidden(R.F64, xn, yn, Pn[0], Pn[1], Pn[2], Pn[3])
+    _bound64(saved[0], h["hx"], "hx")
+    _bound64(saved[1], h["hy"], "hy")
+    assert max(np.abs(hxn).max(), np.abs(hyn).max()) <= R.H_MAX
+    _bound64(out, R.gated_joint_logits(R.F64, hxn, hyn, Pn[4], Pn[5], x_gate)["out"], "out")
+    ws = keep["ws"].cpu().numpy()
+    dhx, dhy = ws[:B * 512].reshape(B, 512), ws[B * 512:].reshape(B, 512)
+    rd = R.gated_joint_dh(R.F64, hxn, hyn, Pn[4], gn, x_gate)
+    _bound64(keep["ws"][:B * 512].view(B, 512), rd["dhx"], "dhx")
+    _bound64(keep["ws"][B * 512:].view(B, 512), rd["dhy"], "dhy")
+    r = R.gated_dx(R.F64, dhx, dhy, Pn[0], Pn[2])
+    _bound64(dx, r["dx"], "dx")
+    _bound64(dy, r["dy"], "dy")
+    r = R.gated_dw1(R.F64, dhx, dhy, xn, yn)
+    gate, val = (hxn, hyn) if x_gate else (hyn, hxn)
+    r.update(R.gated_dwo(R.F64, gate, val, None, None, gn, 0))
+    for k, t, rk in zip(HEAD_NAMES[kind], G, ("dW1", "db1", "dW2", "db2", "dWo", "dbo")):
+        _bound64(t, r[rk], k)
+    # end to end, as before
     D = [p.double() for p in P]
     xd, yd, gd = x.double(), y.double(), go.double()
-    if kind == "sum":
-        ref_out = xd @ D[0].T + D[1] + yd @ D[2].T + D[3]
-        R = [gd.T @ xd, gd.sum(0), gd.T @ yd, gd.sum(0)]
-        rdx, rdy = gd @ D[0], gd @ D[2]
-    else:
-        hx, hy = xd @ D[0].T + D[1], yd @ D[2].T + D[3]
-        gate, val = (hx, hy) if x_gate else (hy, hx)
-        s = torch.sigmoid(gate)
-        m = s * val
-        ref_out = m @ D[4].T + D[5]
-        dm = gd @ D[4]
-        dval, dgate = dm * s, dm * val * s * (1 - s)
-        dhx, dhy = (dgate, dval) if x_gate else (dval, dgate)
-        rdx, rdy = dhx @ D[0], dhy @ D[2]
-        R = [dhx.T @ xd, dhx.sum(0), dhy.T @ yd, dhy.sum(0), gd.T @ m, gd.sum(0)]
+    hx, hy = xd @ D[0].T + D[1], yd @ D[2].T + D[3]
+    gate, val = (hx, hy) if x_gate else (hy, hx)
+    s = torch.sigmoid(gate)
+    m = s * val
+    ref_out = m @ D[4].T + D[5]
+    dm = gd @ D[4]
+    dval, dgate = dm * s, dm * val * s * (1 - s)
+    dhx, dhy = (dgate, dval) if x_gate else (dval, dgate)
+    rdx, rdy = dhx @ D[0], dhy @ D[2]
+    Rp = [dhx.T @ xd, dhx.sum(0), dhy.T @ yd, dhy.sum(0), gd.T @ m, gd.sum(0)]
     _check64(out, ref_out, "out")
     _check64(dx, rdx, "dx")
     _check64(dy, rdy, "dy")
-    for k, t, r in zip(HEAD_NAMES[kind], G, R):
+    for k, t, r in zip(HEAD_NAMES[kind], G, Rp):
         _check64_param(t, r, k)
 
 

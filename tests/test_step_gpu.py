@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import head_ref as R
 from oracle import fixtures as fx
 from oracle import oracle as orc
 
@@ -60,11 +61,14 @@ def test_head_dgl_golden(name, n):
     np.testing.assert_allclose(db.cpu().numpy(), g["db_f"], rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("n", [6, 34, 309])
+@pytest.mark.parametrize("n", [1, 6, 16, 17, 33, 34, 309, 512])
 def test_head_uni_dfeat(n):
     """gdl_head_uni_dfeat (one modality's logits -> alpha * cross-entropy gradient -> feature gradient in one launch) against a
     float64 restatement of main_dgl.py:102-110 for that modality, and bit for bit against the three-launch path it replaces
-    (gdl_head_concat_fwd, gdl_softmax_ce, gdl_head_concat_bwd)."""
+    (gdl_head_concat_fwd, gdl_softmax_ce, gdl_head_concat_bwd).  n = 16 / 17 / 33: the edges of the body's pairing of classes
+    j and j + 16; 512: the most it stages.  The float64 bound (tests/head_ref.py, derived) is held stage by stage on the
+    three-launch path whose bits df carries: the logits, the logit gradient from the device's logits, df from the device's
+    logit gradient."""
     B, alpha = 16, 4.0
     rs = np.random.default_rng(5)
     x, y = rs.standard_normal((B, 512), dtype=np.float32), rs.standard_normal((B, 512), dtype=np.float32)
@@ -87,6 +91,16 @@ def test_head_uni_dfeat(n):
     L.call("gdl_head_uni_dfeat", L.ptr(yd), Wd.data_ptr() + 512 * 4, 1024, L.ptr(bd), L.ptr(ld), alpha, L.ptr(uy), B, n, st)
     torch.cuda.synchronize()
     assert torch.equal(ux.view(torch.int32), dx.view(torch.int32)) and torch.equal(uy.view(torch.int32), dy.view(torch.int32))
+    fw = R.lin_fwd(R.F64, "concat", x, y, W[:, :512], b, W[:, 512:], b)
+    gxn, gyn = gxo.cpu().numpy(), gyo.cpu().numpy()
+    bw = R.lin_bwd(R.F64, "concat", x, y, W[:, :512], W[:, 512:], gxn, gyn, None, 0, 0)
+    for lg, key, gl, dkey, got in ((xo, "x_out", gxn, "dx", ux), (yo, "y_out", gyn, "dy", uy)):
+        lgn = lg.cpu().numpy()
+        ce = R.softmax_ce(R.F64, lgn, lab, alpha)
+        for what, ex in (("logits", R.excess(lgn, *fw[key])), ("dlogits", R.excess(gl, *ce["dlogits"])),
+                         ("df", R.excess(got.cpu().numpy(), *bw[dkey]))):
+            print(key, what, "excess", ex)
+            assert ex <= 1.0, (key, what, "is", ex, "bounds from the float64 value")
     for f, Wm, got in ((x, W[:, :512], ux), (y, W[:, 512:], uy)):
         u = f.astype(np.float64) @ Wm.astype(np.float64).T + b
         p = np.exp(u - u.max(1, keepdims=True))
