@@ -339,6 +339,37 @@ int gdl_journal_append(void* journal, int64_t capacity, const float* losses, int
     return journal_append(journal, capacity, losses, n_losses, stats, out_a, out_v, n_logits, div_a, div_v, ogm,
                           (hipStream_t)stream);
 }
+size_t gdl_eval_bank_bytes(int n_classes, int64_t capacity, int sets) { return eval_bank_bytes(n_classes, capacity, sets); }
+size_t gdl_eval_bank_reset_bytes(int n_classes, int sets) { return eval_bank_reset_bytes(n_classes, sets); }
+// the checks the two score-bank calls share: 0 when the bank can be used as described
+static int eval_bank_check(const char* who, const void* bank, size_t bank_bytes, int n, int64_t capacity, int sets) {
+    GDL_REQUIRE(bank, "%s: null bank", who);
+    GDL_REQUIRE(n >= 1 && n <= 512, "%s: n_classes must be in [1, 512], got %d", who, n);
+    GDL_REQUIRE(sets == 1 || sets == 3, "%s: sets must be 1 (fused alone) or 3 (fused, audio, visual), got %d", who, sets);
+    GDL_REQUIRE(capacity >= 1 && capacity < ((int64_t)1 << 31), "%s: capacity must be in [1, 2^31), got %lld", who,
+                (long long)capacity);
+    GDL_REQUIRE(bank_bytes >= eval_bank_bytes(n, capacity, sets), "%s: a bank of %zu bytes, gdl_eval_bank_bytes asks for %zu", who,
+                bank_bytes, eval_bank_bytes(n, capacity, sets));
+    GDL_REQUIRE(((uintptr_t)bank & 15) == 0, "%s: the bank must be 16-byte aligned", who);
+    return GDL_OK;
+}
+int gdl_eval_bank_append(void* bank, size_t bank_bytes, int n_classes, int64_t capacity, int sets, const float* out,
+                         const float* out_a, const float* out_v, const int64_t* labels, int B, int64_t offset, void* stream) {
+    if (int rc = eval_bank_check("eval_bank_append", bank, bank_bytes, n_classes, capacity, sets)) return rc;
+    GDL_REQUIRE(out && labels, "eval_bank_append: null out or labels");
+    GDL_REQUIRE(sets == 3 || (!out_a && !out_v), "eval_bank_append: a unimodal logit set given to a bank of sets = 1");
+    GDL_REQUIRE(sets == 1 || (out_a && out_v), "eval_bank_append: a bank of sets = 3 needs out_a and out_v");
+    GDL_REQUIRE(B >= 1, "eval_bank_append: B must be at least 1, got %d", B);
+    GDL_REQUIRE(offset >= 0 && offset + B <= capacity, "eval_bank_append: rows %lld .. %lld do not fit a capacity of %lld",
+                (long long)offset, (long long)offset + B - 1, (long long)capacity);
+    return eval_bank_append(bank, n_classes, capacity, sets, out, out_a, out_v, labels, B, offset, (hipStream_t)stream);
+}
+int gdl_eval_bank_ap(void* bank, size_t bank_bytes, int n_classes, int64_t capacity, int sets, int64_t N, void* stream) {
+    if (int rc = eval_bank_check("eval_bank_ap", bank, bank_bytes, n_classes, capacity, sets)) return rc;
+    GDL_REQUIRE(N >= 0 && N <= capacity, "eval_bank_ap: N = %lld samples in a bank of capacity %lld", (long long)N,
+                (long long)capacity);
+    return eval_bank_ap(bank, n_classes, capacity, sets, N, (hipStream_t)stream);
+}
 size_t gdl_head_mtl_ce_workspace_bytes(int B) { return head_mtl_ce_ws_bytes(B); }
 int gdl_head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,
                     int sum_bias, const int64_t* labels, float scale_u, int fused_reaches, float* out, float* out_a, float* out_v,

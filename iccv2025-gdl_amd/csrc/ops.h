@@ -187,6 +187,12 @@ size_t journal_bytes(int64_t capacity);
 int journal_append(void* journal, int64_t capacity, const float* losses, int n_losses, const float* stats, const float* out_a,
                    const float* out_v, int64_t n_logits, const float* div_a, const float* div_v, const float* ogm,
                    hipStream_t st);
+// evalbank.hip: the evaluation report's score bank (softmax scores, ranks, confusion per batch; average precision at the end)
+size_t eval_bank_bytes(int n, int64_t capacity, int sets);
+size_t eval_bank_reset_bytes(int n, int sets);
+int eval_bank_append(void* bank, int n, int64_t capacity, int sets, const float* out, const float* out_a, const float* out_v,
+                     const int64_t* labels, int B, int64_t offset, hipStream_t st);
+int eval_bank_ap(void* bank, int n, int64_t capacity, int sets, int64_t N, hipStream_t st);
 int head_concat_fwd(const float* x, const float* y, const float* W, const float* b, float* out, float* x_out, float* y_out,
                     int B, int n, hipStream_t st);
 int head_concat_bwd(const float* x, const float* y, const float* W, const float* g_x_out, const float* g_y_out,

@@ -13,7 +13,12 @@ def __getattr__(name):
     feature map, and `gdl.journal`, the step journal's module (`gdl.journal.COLUMNS`), and the device-side waveform staging of
     gdl.data (`gdl.stage_audio`, `gdl.wave_log_spectrogram`, `gdl.wave_descriptors`, `gdl.pack_clips`, `gdl.wave_limit`,
     `gdl.random_wave_starts`, `gdl.AUDIO_STAGES`), and the linear probe of gdl.probe (`gdl.extract_features`, `gdl.FeatureBank`,
-    `gdl.LinearProbe`, `gdl.probe_order`, `gdl.multistep_lr`) -- imported on first use (they import torch)."""
+    `gdl.LinearProbe`, `gdl.probe_order`, `gdl.multistep_lr`), and `gdl.ScoreBank`, the evaluation report of gdl.evaluate (mAP,
+    top-k, confusion) -- imported on first use (they import torch)."""
+    if name == "ScoreBank":
+        from .evaluate import ScoreBank
+
+        return ScoreBank
     if name in ("stage_audio", "wave_log_spectrogram", "wave_descriptors", "pack_clips", "wave_limit", "random_wave_starts", "AUDIO_STAGES"):
         from . import data
 

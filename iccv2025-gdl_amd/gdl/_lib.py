@@ -116,6 +116,10 @@ SIGNATURES = {
     "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),
     "gdl_journal_bytes": ("z", "l"),
     "gdl_journal_append": ("i", "pl" + "pi" + "p" + "ppl" + "pp" + "p" + "p"),
+    "gdl_eval_bank_bytes": ("z", "ili"),
+    "gdl_eval_bank_reset_bytes": ("z", "ii"),
+    "gdl_eval_bank_append": ("i", "pz" + "ili" + "pppp" + "il" + "p"),
+    "gdl_eval_bank_ap": ("i", "pz" + "ili" + "l" + "p"),
     "gdl_head_concat_fwd": ("i", "ppppppp" + "ii" + "p"),
     "gdl_head_concat_bwd": ("i", "pppppp" + "ii" + "pppp" + "ii" + "p"),
     "gdl_softmax_ce": ("i", "ppf" + "pp" + "ii" + "p"),

@@ -206,11 +206,15 @@ class LinearProbe:
         self.epoch += epochs
         return [float(s / c) if c else float("nan") for s, c in a]
 
-    def score(self, bank, chunk=4096):
+    def score(self, bank, chunk=4096, scores=None):
         """(accuracy, counts [2, n] int64: per class the samples seen and the samples right) of arg-max(f W^T + b) over the
-        bank; the first maximum wins, as np.argmax.  gdl_head_cls_fwd in chunks + gdl_eval_count, one host copy."""
+        bank; the first maximum wins, as np.argmax.  gdl_head_cls_fwd in chunks + gdl_eval_count, one host copy.
+        scores: a gdl.ScoreBank of sets = 1 that every chunk is appended to behind its counters (mAP / top-k / confusion from
+        `scores.report()`), refused before the first launch if it does not fit; the return value does not change."""
         self._check_bank(bank)
         n = self.n_classes
+        if scores is not None:
+            scores.check(n, 1, self.device, bank.N, "LinearProbe.score")
         with torch.cuda.device(self.device):
             cnt = torch.zeros((2, n), dtype=torch.int64, device=self.device)
             out = torch.empty((min(chunk, bank.N), n), device=self.device)
@@ -221,6 +225,8 @@ class LinearProbe:
                        FEAT, st)
                 L.call("gdl_eval_count", L.ptr(out), None, None, bank.labels[o:o + B].data_ptr(), B, n, cnt[0].data_ptr(),
                        cnt[1].data_ptr(), None, None, st)
+                if scores is not None:
+                    scores.append(out[:B], None, None, bank.labels[o:o + B], stream=st)
             c = cnt.cpu().numpy()
         return float(c[1].sum()) / max(float(c[0].sum()), 1.0), c
 

@@ -961,11 +961,17 @@ class DGLTrainer(ArenaTrainer):
                    B, n, st)
 
     # ------------------------------------------------------------------ validation (main_dgl.py:168-222)
-    def valid(self, batches):
+    def valid(self, batches, bank=None):
         """The reference's valid(): eval-mode forward (BatchNorm running statistics) of every (spec, image, label)
         batch, arg-max of the three logit sets and per-class counters -- all on the device, one host copy at the
-        end instead of 3*B per batch.  Returns (acc, acc_a, acc_v) = sum(acc*)/sum(num) as main_dgl.py:222."""
+        end instead of 3*B per batch.  Returns (acc, acc_a, acc_v) = sum(acc*)/sum(num) as main_dgl.py:222.
+        bank: a gdl.ScoreBank (sets = 3 in the DGL mode, 1 for mode="joint") that every batch is appended to behind its
+        counters, for mAP / top-k / confusion from `bank.report()`; the return value and `valid_counts` do not change.  A bank
+        of another class count, set count or device, or without room for every batch, is refused before the first launch."""
         n = self.n_classes
+        if bank is not None:
+            batches = list(batches)
+            bank.check(n, 3 if self.mode == "dgl" else 1, self.device, sum(int(b[2].shape[0]) for b in batches), "DGLTrainer.valid")
         cnt = torch.zeros((4, n), dtype=torch.int64, device=self.device)
         main = torch.cuda.current_stream(self.device)
         self.sync_replicas()  # data-parallel: evaluate with rank 0's running statistics (SURVEY 8(e) "Buffers")
@@ -990,6 +996,8 @@ class DGLTrainer(ArenaTrainer):
             L.call("gdl_eval_count", L.ptr(self.out), L.ptr(self.out_a) if dgl else None, L.ptr(self.out_v) if dgl else None,
                    L.ptr(label), self.B, n, cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr() if dgl else None,
                    cnt[3].data_ptr() if dgl else None, st)
+            if bank is not None:
+                bank.append(self.out, self.out_a if dgl else None, self.out_v if dgl else None, label, stream=st)
         c = cnt.cpu().numpy().astype("float64")
         self.valid_counts = c
         tot = max(c[0].sum(), 1.0)

@@ -138,11 +138,16 @@ class UnimodalTrainer(ArenaTrainer):
         caller.wait_stream(main)
 
     # ------------------------------------------------------------------ validation (main.py's valid())
-    def valid(self, batches):
+    def valid(self, batches, bank=None):
         """Eval-mode forward (BatchNorm running statistics) of every (spec, image, label) batch, arg-max of `out` and the
         per-class counters on the device, one host copy at the end.  The reference's valid() counts its three (identical) logit
-        sets: returns (acc, acc, acc); `valid_counts` rows = num, acc, acc, acc per class."""
+        sets: returns (acc, acc, acc); `valid_counts` rows = num, acc, acc, acc per class.
+        bank: a gdl.ScoreBank of sets = 1 that every batch is appended to behind its counters (mAP / top-k / confusion from
+        `bank.report()`), refused before the first launch if it does not fit; nothing else changes."""
         n = self.n_classes
+        if bank is not None:
+            batches = list(batches)
+            bank.check(n, 1, self.device, sum(int(b[2].shape[0]) for b in batches), "UnimodalTrainer.valid")
         cnt = torch.zeros((2, n), dtype=torch.int64, device=self.device)
         for spec, image, label in batches:
             x = self._input(spec, image)
@@ -156,6 +161,8 @@ class UnimodalTrainer(ArenaTrainer):
                    512, st)
             L.call("gdl_eval_count", L.ptr(self.out), None, None, L.ptr(label), self.B, n, cnt[0].data_ptr(), cnt[1].data_ptr(),
                    None, None, st)
+            if bank is not None:
+                bank.append(self.out, None, None, label, stream=st)
         c = cnt.cpu().numpy().astype("float64")
         self.valid_counts = c[[0, 1, 1, 1]]
         acc = c[1].sum() / max(c[0].sum(), 1.0)

@@ -700,6 +700,52 @@ GDL_API int gdl_journal_append(void* journal, int64_t capacity, const float* los
                                const float* out_a, const float* out_v, int64_t n_logits, const float* div_a, const float* div_v,
                                const float* ogm, void* stream);
 
+/* ------------------------------------------------------------------ evaluation report: the score bank
+ * What the papers' tables give beyond valid()'s three accuracies -- mAP, top-k, the confusion matrices of the fused / audio /
+ * visual logit sets -- computed on the device: one launch per batch behind gdl_eval_count, one launch pair and ONE host copy at
+ * the end.  Not a port of a reference script (its valid() stops at the accuracies).  All state lives in one caller-owned
+ * device buffer of gdl_eval_bank_bytes(n_classes, capacity, sets) bytes, 16-byte aligned; n_classes <= 512, sets = 1 (the fused
+ * set alone) or 3 (fused, audio, visual), capacity = samples it can hold (< 2^31).  The caller keeps the append offset.
+ *   byte 0             int64  skipped              samples whose label lies outside [0, n)
+ *   byte 8             int64  nonfinite[3]         per set: rows holding a NaN / inf logit (samples with a valid label only)
+ *   byte 32            int64  num[n]               samples per class (valid labels)
+ *   + 8 n              int64  rank_hist[sets][n]   [s][r]: samples whose label has rank r in set s; top-k = sum over r < k
+ *   + 8 sets n         int64  confusion[sets][n][n]  row = label, column = prediction
+ *   ---- gdl_eval_bank_reset_bytes(n, sets) = 32 + 8 n (1 + sets + sets n): everything above.  Zero it (hipMemsetAsync on the
+ *        stream) before the first append and for a new report; nothing below needs clearing.
+ *   then               double ap[sets][n]          gdl_eval_bank_ap's result; NaN for a class without a positive
+ *   then               double mAP[3], 8 bytes of padding
+ *   then (16-aligned)  int32  labels[capacity]     -1 for a skipped sample; the array is rounded up to 16 bytes
+ *   then               float  probs[sets][n][capacity]   class-major: one class's scores over all samples are contiguous
+ * gdl_eval_bank_append -- rows offset .. offset + B - 1 from out / out_a / out_v [B, n] and int64 labels[B], one launch, per
+ * sample and set: the float32 softmax (row maximum; expf(l - max); their sum in ascending class order; lse = max + logf(sum);
+ * p = expf(l - lse)) stored transposed into probs; the prediction (first maximum of the logits, strict >, as gdl_eval_count);
+ * the label's rank  #{j : l_j > l_lab} + #{j < lab : l_j == l_lab}  (rank 0 is the event prediction == label);
+ * rank_hist[s][rank] += 1, confusion[s][label][prediction] += 1, num[label] += 1 (64-bit integer atomics: order-free; there is
+ * no floating-point atomic).  A label outside [0, n), range-checked at 64 bits: labels[row] = -1, skipped += 1, NaN in the
+ * row's probs, nothing else.  A row with a non-finite logit: nonfinite[s] += 1, NaN in that set's probs of the row, and no
+ * rank_hist / confusion entry and no part in the average precision of that set.
+ * gdl_eval_bank_ap -- over the first N rows, per class c and set s, scikit-learn's average_precision_score (step-wise, ties
+ * grouped) on the stored float32 probabilities, without a sort:
+ *     ap[s][c] = (1 / |pos_c|) sum_{i in pos_c}  #{j : label_j = c, p_jc >= p_ic} / #{j : p_jc >= p_ic}
+ * j over the samples with a valid label and a finite row in set s.  Probabilities are compared by their bit patterns as
+ * unsigned integers (they are non-negative: the float order, whatever the denormal mode); both counts are exact integers, each
+ * quotient one float64 division, the quotients added in ascending sample order, one division by |pos_c|: within
+ * (|pos_c| + 2) 2^-53 of the exact rational value.  A class without a positive gives NaN (scikit-learn: 0.0 and a warning).
+ * mAP[s] = the float64 mean of the non-NaN classes in class order (NaN if there is none).  No block waits for another and
+ * nothing is accumulated across blocks: two calls give identical bytes.
+ * Calls on one bank must be ordered on one stream, behind whatever writes the logits.  GDL_ERR_ARG, with a message and without
+ * a launch: bank NULL or not 16-byte aligned; n_classes outside [1, 512]; sets not 1 or 3; capacity outside [1, 2^31);
+ * bank_bytes below gdl_eval_bank_bytes; out or labels NULL; out_a / out_v given with sets = 1 or missing with sets = 3; B < 1;
+ * offset < 0 or offset + B > capacity; N outside [0, capacity].  gdl_eval_bank_bytes / gdl_eval_bank_reset_bytes: 0 for such
+ * a shape. */
+GDL_API size_t gdl_eval_bank_bytes(int n_classes, int64_t capacity, int sets);
+GDL_API size_t gdl_eval_bank_reset_bytes(int n_classes, int sets);
+GDL_API int gdl_eval_bank_append(void* bank, size_t bank_bytes, int n_classes, int64_t capacity, int sets, const float* out,
+                                 const float* out_a, const float* out_v, const int64_t* labels, int B, int64_t offset,
+                                 void* stream);
+GDL_API int gdl_eval_bank_ap(void* bank, size_t bank_bytes, int n_classes, int64_t capacity, int sets, int64_t N, void* stream);
+
 /* ------------------------------------------------------------------ linear probe of a frozen encoder
  * One epoch of the linear probe's fit: main.py's unimodal step with the encoder removed, on features that are already on the
  * device.  bank [N][512] float32 (the pooled features of an eval-mode encoder), labels [N] int64, order [steps][B] int32 (device):
