@@ -560,3 +560,86 @@ def test_swin_backward_phases_equal_whole(cfg_name):
     torch.cuda.synchronize()
     for n, a, b in zip(names, whole, two):
         assert torch.equal(a, b), n
+
+
+def _tiny2(dtype):
+    """An eager SWIN_TINY2 engine for 2 x 2 frames -- the smallest shape with every fold site (a norm1 carrying the block
+    below's fc2 row, a stage-last block below the last stage, the final norm, patch merging, the patch embedding) -- with
+    its parameters, an input, an upstream gradient and DropPath scales that hold zeros and 1 / keep in every block / branch."""
+    from gdl.swin import SwinEngine
+
+    cfg = fx.SWIN_TINY2
+    eng = SwinEngine(cfg, dtype, 2, 2, DEV)
+    eng.use_graph = False
+    params = [torch.from_numpy(v).to(DEV) for v in fx.make_state(fx.swin_param_shapes(cfg)).values()]
+    eng.set_params(params)
+    x = torch.from_numpy(fx.swin_input(cfg, 2, 2, 5)).to(DEV)
+    dy = torch.from_numpy(np.random.default_rng(3).standard_normal((4, eng.C_out), dtype=np.float32)).to(DEV)
+    k, br, f = np.meshgrid(np.arange(4), np.arange(2), np.arange(4), indexing="ij")
+    scales = np.where((k + br + f) % 2 == 0, 2.0, 0.0).astype(np.float32)  # keep probability 1 / 2
+    assert all(set(scales[i, j]) == {0.0, 2.0} for i in range(4) for j in range(2))
+    return eng, params, x, dy, torch.from_numpy(scales).to(DEV)
+
+
+def _backward(eng, params, dy, phases):
+    grads = [torch.full_like(p, float("nan")) for p in params]
+    for ph in phases:
+        eng.backward(dy, grads, phase=ph)
+    torch.cuda.synchronize()
+    return grads
+
+
+@pytest.mark.parametrize("drop", [False, True])
+@pytest.mark.parametrize("dtype", ["bf16", "f32"])
+def test_swin_deferred_folds_equal_per_call_folds(monkeypatch, dtype, drop):
+    """The fold plan made at construction (one gdl_swin_partial_reduce_batched launch per backward body, a table per part
+    and DropPath mode) against a fold launch behind every LayerNorm backward / column-sum pass (GDL_SWIN_DEFER_FOLDS=0):
+    the same gradients bit for bit, from the whole backward and from phases 1 + 2."""
+    for k in ("GDL_TUNING", "GDL_SWIN_DEFER_FOLDS"):
+        monkeypatch.delenv(k, raising=False)
+    eng, params, x, dy, scales = _tiny2(dtype)
+    monkeypatch.setenv("GDL_TUNING", "1")
+    monkeypatch.setenv("GDL_SWIN_DEFER_FOLDS", "0")
+    per_call = _tiny2(dtype)[0]
+    assert eng.defer_folds and not per_call.defer_folds
+    sc = scales if drop else None
+    eng.forward(x, drop_scales=sc)
+    whole = _backward(eng, params, dy, (0,))
+    eng.forward(x, drop_scales=sc)
+    phased = _backward(eng, params, dy, (1, 2))
+    per_call.forward(x, drop_scales=sc)
+    want = _backward(per_call, params, dy, (0,))
+    for (n, _), w, a, b in zip(eng.param_shapes(), want, whole, phased):
+        assert torch.isfinite(w).all(), n
+        assert torch.equal(w, a), n
+        assert torch.equal(w, b), n
+
+
+@pytest.mark.parametrize("phases,drop", [((0,), False), ((1, 2), True)])
+def test_swin_bodies_allocate_nothing(phases, drop):
+    """The first forward and the first backward an engine ever runs allocate no device memory: every partial buffer, gather
+    table and fold table is made by the constructor (the tables of the caller's parameter / gradient pointers are made by the
+    first _pack_all / _unpack_all with those pointers -- here in advance)."""
+    eng, params, x, dy, scales = _tiny2("bf16")
+    grads = [torch.full_like(p, float("nan")) for p in params]
+    st = L.cur_stream()
+    eng._pack_all(st)
+    for part in ((None,) if phases == (0,) else ("last", "rest")):
+        eng._unpack_all(grads, st, part)
+    torch.cuda.synchronize()
+    before = (torch.cuda.memory_stats(DEV)["allocation.all.allocated"], torch.cuda.memory_allocated(DEV))
+    eng.forward(x, drop_scales=scales if drop else None)
+    for ph in phases:
+        eng.backward(dy, grads, phase=ph)
+    torch.cuda.synchronize()
+    assert (torch.cuda.memory_stats(DEV)["allocation.all.allocated"], torch.cuda.memory_allocated(DEV)) == before
+    assert all(torch.isfinite(g).all() for g in grads)
+
+
+@pytest.mark.parametrize("change", [dict(heads=(3, 4)), dict(img=58)])
+def test_swin_engine_refuses_bad_configuration(change):
+    """Head dimension other than 32, an image that is no whole number of patches: GdlError from the constructor."""
+    from gdl.swin import SwinEngine
+
+    with pytest.raises(L.GdlError):
+        SwinEngine({**fx.SWIN_TINY2, **change}, "bf16", 2, 2, DEV)

@@ -13,8 +13,8 @@ for dtype in ('f32','bf16'):
     print(dtype,'y finite',torch.isfinite(y).all().item(), float(y.abs().mean()))
     def chk(name,t): print('   ',name, torch.isfinite(t.float()).all().item(), float(t.float().abs().mean()))
     chk('pe_rows',eng.pe_rows); chk('pe_out',eng.pe_out); chk('x0',eng.x0)
-    b=eng.stages[0]['blocks'][0]
-    for k in ('h','qkv_a','attn','x_mid','m','u','a','x_out'): chk(k,b[k])
+    b=eng.stages[0].blocks[0]
+    for k in ('h','qkv_a','attn','x_mid','m','u','a','x_out'): chk(k,getattr(b,k))
     grads=[torch.full_like(p,float('nan')) for p in params]
     eng.backward(torch.randn(4,192,device=DEV),grads); torch.cuda.synchronize()
     bad=[n for (n,_),g in zip(eng.param_shapes(),grads) if not torch.isfinite(g).all()]
