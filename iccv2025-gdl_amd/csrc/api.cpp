@@ -308,6 +308,32 @@ int gdl_linprobe_epoch(const float* bank, const int64_t* labels, int64_t N, cons
     return linprobe_epoch(bank, labels, N, order, steps, B, W, b, mW, mb, n_classes, lr, momentum, weight_decay, max_norm, loss_acc,
                           ws, (hipStream_t)stream);
 }
+int gdl_proto_ce(const float* f, const float* P, const int64_t* labels, float* u, float* terms, float* sim, int B, int n_classes,
+                 int width, void* stream) {
+    GDL_REQUIRE(width == 512, "proto_ce: feature width %d (the prototypes are built for 512)", width);
+    GDL_REQUIRE(n_classes >= 1 && n_classes <= 512, "proto_ce: n_classes must be in [1, 512], got %d", n_classes);
+    GDL_REQUIRE(B >= 1, "proto_ce: B must be at least 1, got %d", B);
+    GDL_REQUIRE(f && P && labels && u && terms, "proto_ce: null argument (only sim may be NULL)");
+    return proto_ce(f, P, labels, u, terms, sim, B, n_classes, (hipStream_t)stream);
+}
+int gdl_proto_apply(const float* terms_a, const float* terms_v, const float* u_a, const float* u_v, float* dfa, float* dfv,
+                    float alpha, float* stats, int B, int width, void* stream) {
+    GDL_REQUIRE(width == 512, "proto_apply: feature width %d (the prototypes are built for 512)", width);
+    GDL_REQUIRE(B >= 1 && B <= (1 << 22), "proto_apply: B must be in [1, 2^22], got %d", B);
+    GDL_REQUIRE(terms_a && terms_v && u_a && u_v && dfa && dfv && stats, "proto_apply: null argument");
+    GDL_REQUIRE((((uintptr_t)u_a | (uintptr_t)u_v | (uintptr_t)dfa | (uintptr_t)dfv) & 15) == 0,
+                "proto_apply: u_a, u_v, dfa and dfv must be 16-byte aligned");
+    return proto_apply(terms_a, terms_v, u_a, u_v, dfa, dfv, alpha, stats, B, (hipStream_t)stream);
+}
+int gdl_proto_update(const float* bank, const int64_t* labels, int64_t N, float* P, int n_classes, int width, double momentum,
+                     int first, int64_t* count, int64_t* info, void* stream) {
+    GDL_REQUIRE(width == 512, "proto_update: feature width %d (the prototypes are built for 512)", width);
+    GDL_REQUIRE(n_classes >= 1 && n_classes <= 512, "proto_update: n_classes must be in [1, 512], got %d", n_classes);
+    GDL_REQUIRE(N >= 1, "proto_update: N must be at least 1, got %lld", (long long)N);
+    GDL_REQUIRE(momentum >= 0.0 && momentum <= 1.0, "proto_update: momentum must be in [0, 1], got %g", momentum);
+    GDL_REQUIRE(bank && labels && P && count && info, "proto_update: null argument");
+    return proto_update(bank, labels, N, P, n_classes, momentum, first != 0, count, info, (hipStream_t)stream);
+}
 size_t gdl_feature_diversity_workspace_bytes(int n_img) { return feature_diversity_ws_bytes(n_img); }
 int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int P, int C, float* per_image, float* mean_out,
                           float* accum, void* ws, size_t ws_bytes, void* stream) {

@@ -173,6 +173,12 @@ size_t linprobe_ws_bytes(int B, int n);
 int linprobe_epoch(const float* bank, const int64_t* labels, int64_t N, const int32_t* order, int steps, int B, float* W, float* b,
                    float* mW, float* mb, int n, float lr, float mu, float wd, float max_norm, double* loss_acc, void* ws,
                    hipStream_t st);
+// proto.hip: prototypical modal rebalance on pooled [B][512] features (prototype cross-entropy, the coefficient rule, the bank pass)
+int proto_ce(const float* f, const float* P, const int64_t* labels, float* u, float* terms, float* sim, int B, int n, hipStream_t st);
+int proto_apply(const float* terms_a, const float* terms_v, const float* u_a, const float* u_v, float* dfa, float* dfv, float alpha,
+                float* stats, int B, hipStream_t st);
+int proto_update(const float* bank, const int64_t* labels, int64_t N, float* P, int n, double momentum, int first, int64_t* count,
+                 int64_t* info, hipStream_t st);
 // head_mtl.hip: the one-launch junction of the step whose fused loss reaches the encoders (concat / sum DGL head, un-detached)
 size_t head_mtl_ce_ws_bytes(int B);
 int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,

@@ -14,7 +14,12 @@ def __getattr__(name):
     gdl.data (`gdl.stage_audio`, `gdl.wave_log_spectrogram`, `gdl.wave_descriptors`, `gdl.pack_clips`, `gdl.wave_limit`,
     `gdl.random_wave_starts`, `gdl.AUDIO_STAGES`), and the linear probe of gdl.probe (`gdl.extract_features`, `gdl.FeatureBank`,
     `gdl.LinearProbe`, `gdl.probe_order`, `gdl.multistep_lr`), and `gdl.ScoreBank`, the evaluation report of gdl.evaluate (mAP,
-    top-k, confusion) -- imported on first use (they import torch)."""
+    top-k, confusion), and the class prototypes of gdl.prototypes (`gdl.Prototypes`, `gdl.prototype_logits`: prototypical modal
+    rebalance on the joint step) -- imported on first use (they import torch)."""
+    if name in ("Prototypes", "prototype_logits"):
+        from . import prototypes
+
+        return getattr(prototypes, name)
     if name == "ScoreBank":
         from .evaluate import ScoreBank
 

@@ -111,6 +111,9 @@ SIGNATURES = {
     "gdl_head_mtl_ce": ("i", "pppp" + "i" + "pp" + "i" + "p" + "fi" + "ppp" + "p" + "ppp" + "pp" + "ii" + "pz" + "p"),
     "gdl_linprobe_workspace_bytes": ("z", "ii"),
     "gdl_linprobe_epoch": ("i", "ppl" + "pii" + "pppp" + "i" + "ffff" + "p" + "pz" + "p"),
+    "gdl_proto_ce": ("i", "pppppp" + "iii" + "p"),
+    "gdl_proto_apply": ("i", "pppppp" + "f" + "p" + "ii" + "p"),
+    "gdl_proto_update": ("i", "ppl" + "p" + "ii" + "d" + "i" + "pp" + "p"),
     "gdl_feature_diversity_workspace_bytes": ("z", "i"),
     "gdl_feature_diversity": ("i", "p" + "iiiii" + "ppp" + "pz" + "p"),
     "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),

@@ -24,6 +24,9 @@ every data-parallel run):
 Joint step with modulation="OGM" / "OGM_GE" (main.py:286-330; concat and sum heads): gdl_head_uni_scores behind the head forward
 (the unimodal scores, on the device), and gdl_optim_modulate between the statistics and the update -- the convolution weight
 gradients of both encoders become (g k) c [+ sigma z] in the arena, the update takes the arena as it stands.
+Joint step with `prototypes=` (prototypical modal rebalance, gdl.prototypes; all four heads): gdl_proto_ce behind each encoder's
+forward on its own stream, gdl_proto_apply behind the head's feature gradients in front of the junction event -- the feature
+gradient of the modality that is behind gains alpha * d lossp / d feature, nothing else changes.
 
 DGL ablations (mode="dgl"; `detach_fused`, `drop_head_uni`): DGL is two truncations of one three-loss step -- the fused logits are
 detached (main_dgl.py:100-108, the .detach() inside every *_DGL head) and the unimodal losses' gradients in the fusion module are
@@ -412,7 +415,7 @@ class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
                  modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True,
-                 diversity=False, journal=0):
+                 diversity=False, journal=0, prototypes=None):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
@@ -439,10 +442,22 @@ class DGLTrainer(ArenaTrainer):
         loss_v are whatever `read()` reports); the diversity columns need diversity=True, the OGM columns a modulated step.
         Every form of the step, the Swin composition and a process group are allowed: with a group the losses and logits are
         the LOCAL rank's and the gradient statistics those of the reduced gradient.  0 (the default): nothing is allocated or
-        launched and the step is bit for bit what it was.  Not part of `state_dict()`."""
+        launched and the step is bit for bit what it was.  Not part of `state_dict()`.
+        prototypes: a gdl.Prototypes -- prototypical modal rebalance (PMR, CVPR 2023) on the joint step
+        (mode="joint", any of the four heads, ResNet18 encoders, modulation="Normal", no process group).  While
+        modulation_starts <= self.epoch <= modulation_ends the step adds beta lossp_a + lam lossp_v to CE(out): lossp_m is the
+        cross-entropy of the negated Euclidean distances from encoder m's pooled feature to the class prototypes, and only the
+        modality whose summed label probability is behind gets a non-zero coefficient, `alpha`.  gdl_proto_ce runs behind each
+        encoder's training forward on that encoder's stream, gdl_proto_apply adds alpha u to that side's feature gradient on the
+        main stream between the head's feature gradients and the junction event; the other side's gradient, the head's parameter
+        gradients, the logits and `loss_f` (= CE(out)) are those of the plain joint step bit for bit.  `read()` gains `pmr` =
+        {score_a, score_v, rho, beta, lam, lossp_a, lossp_v}; the journal's columns are unchanged.  The caller refreshes the
+        prototypes once per epoch (`prototypes.update`).  Outside the window, or without prototypes, nothing is allocated or
+        launched.  `state_dict()` carries the prototypes' state when they are attached."""
         self._check_optimizer(optimizer)
         self._check_modulation(modulation)
         self._check_journal(journal)
+        self._check_prototypes(prototypes, mode, modulation, process_group)
         self.model = model
         self.mode = mode
         self.alpha = float(alpha)
@@ -515,6 +530,17 @@ class DGLTrainer(ArenaTrainer):
         self.vis_swin = hasattr(model.visual_net, "cfg") and hasattr(model.visual_net, "num_features")
         self.nv = len(named) - nf - 60
         self.dv = int(model.visual_net.num_features) if self.vis_swin else 512
+        self.prototypes = prototypes
+        self._pmr_now = False
+        self._pmr_B = None  # the batch size the step's PMR buffers were allocated for (None: none yet)
+        if prototypes is not None:
+            if self.vis_swin:
+                raise L.GdlError("DGLTrainer: prototypes are not built for the Swin visual branch (768 features; the prototypes "
+                                 "are 512 wide)")
+            if prototypes.n_classes != self.n_classes:
+                raise L.GdlError(f"DGLTrainer: the prototypes hold {prototypes.n_classes} classes, the model's head {self.n_classes}")
+            if prototypes.device != device:
+                raise L.GdlError(f"DGLTrainer: the prototypes are on {prototypes.device}, the model on {device}")
         if self.vis_swin and (self.head != "concat" or mode != "dgl"):
             raise L.GdlError("DGLTrainer: the Swin visual branch is built for the concat DGL head")
         if not self.vis_swin and self.nv != 60:
@@ -584,6 +610,26 @@ class DGLTrainer(ArenaTrainer):
         self._setup_journal(journal, self.mode == "dgl")
         self.eng_a = self.eng_v = None
 
+    @staticmethod
+    def _check_prototypes(prototypes, mode, modulation, process_group):
+        """(like `_check_optimizer`: before the model is touched) what prototypical modal rebalance is not built for is refused,
+        never ignored; the checks against the model -- class count, device, the Swin branch -- follow once the head is known."""
+        if prototypes is None:
+            return
+        from .prototypes import Prototypes
+
+        if not isinstance(prototypes, Prototypes):
+            raise L.GdlError(f"DGLTrainer: prototypes must be a gdl.Prototypes, got {type(prototypes).__name__}")
+        if mode == "dgl":
+            raise L.GdlError("DGLTrainer: prototypes belong to the joint step (mode=\"joint\"); the DGL step has no fused loss in "
+                             "its encoders for the prototype term to rebalance")
+        if modulation != "Normal":
+            raise L.GdlError(f"DGLTrainer: prototypes with modulation={modulation!r} are not built (two rebalancing methods in one "
+                             "step); modulation must be \"Normal\"")
+        if process_group is not None:
+            raise L.GdlError("DGLTrainer: prototypes with a process group are not supported (the scores are sums over the global "
+                             "batch and would need a collective of their own)")
+
     def _journal_logits(self):
         return (self.out_a, self.out_v) if self.mode == "dgl" else (None, None)
 
@@ -610,6 +656,8 @@ class DGLTrainer(ArenaTrainer):
             sd.update(modulation=self.modulation, seed=self.seed)
         if self.ablation:  # (the arena's composition and the step depend on them)
             sd.update(detach_fused=self.detach_fused, drop_head_uni=self.drop_head_uni)
+        if self.prototypes is not None:  # (the step's loss depends on them; they carry an epoch-to-epoch momentum)
+            sd["prototypes"] = self.prototypes.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -621,7 +669,12 @@ class DGLTrainer(ArenaTrainer):
         if sw != (self.detach_fused, self.drop_head_uni):
             raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint was trained with detach_fused={sw[0]}, drop_head_uni={sw[1]}, "
                              f"this trainer runs detach_fused={self.detach_fused}, drop_head_uni={self.drop_head_uni}")
+        if ("prototypes" in sd) != (self.prototypes is not None):
+            raise L.GdlError("DGLTrainer.load_state_dict: the checkpoint was trained " + ("with" if "prototypes" in sd else "without") +
+                             " prototypes, this trainer runs " + ("without" if "prototypes" in sd else "with") + " them")
         super().load_state_dict(sd)
+        if self.prototypes is not None:
+            self.prototypes.load_state_dict(sd["prototypes"])
         if self._mod is not None:  # the noise continues the checkpoint's stream: its key, and the step count loaded above
             self.seed = int(sd.get("seed", self.seed))
             self._mod = self._mod[:2] + (self.seed,)
@@ -772,12 +825,19 @@ class DGLTrainer(ArenaTrainer):
                     red.launch("visual_rest")
             self._finish_step(main, st)
             return
+        pmr = self._pmr_now = (self.prototypes is not None and self.modulation_starts <= self.epoch <= self.modulation_ends)
+        if pmr:
+            self._pmr_buffers()
         with torch.cuda.stream(self.s_v):
             self.eng_v.forward(image, True, feat_out=self.fv)
             self._diversity(self.eng_v, 1)
+            if pmr:
+                self._proto_ce(1, self.fv, label, self.s_v.cuda_stream)
         with torch.cuda.stream(self.s_a):
             self.eng_a.forward(audio, True, feat_out=self.fa)
             self._diversity(self.eng_a, 0)
+            if pmr:
+                self._proto_ce(0, self.fa, label, self.s_a.cuda_stream)
         main.wait_stream(self.s_a)
         main.wait_stream(self.s_v)
         self._mark(main, "fwd_done")
@@ -808,6 +868,12 @@ class DGLTrainer(ArenaTrainer):
             # of the audio backward; the visual chain, the critical path, starts as soon as dfa / dfv exist.  Same kernels, same
             # numbers.  With a process group the fusion bucket's collective is launched at the junction: everything first.
             self._joint_head_backward(st, True, red is not None)
+            if pmr:
+                # prototypical modal rebalance: dfa += beta u_a, dfv += lam u_v (one of the two, chosen on the device from the
+                # scores), behind the head's feature gradients and in front of the junction event -- the one launch PMR adds to
+                # the critical path; the two gdl_proto_ce ran behind the forwards on the encoders' own streams
+                L.call("gdl_proto_apply", L.ptr(self.pmr_terms[0]), L.ptr(self.pmr_terms[1]), L.ptr(self.pmr_u[0]),
+                       L.ptr(self.pmr_u[1]), L.ptr(self.dfa), L.ptr(self.dfv), self.alpha, L.ptr(self.pmr_stats), B, 512, st)
         self._mark(main, "head_done")
         if red is not None:
             red.launch("fusion")
@@ -830,6 +896,21 @@ class DGLTrainer(ArenaTrainer):
             with torch.cuda.stream(self.s_v):
                 red.launch("visual_rest")
         self._finish_step(main, st)
+
+    def _pmr_buffers(self):
+        """What a step with the prototype term writes besides the step's own tensors, allocated at the first such step (and
+        again for another batch size): u [2, B, 512], the samples' terms [2, 2, B], stats [8]."""
+        if self._pmr_B != self.B:
+            d = self.device
+            self.pmr_u = torch.empty((2, self.B, 512), device=d)
+            self.pmr_terms = torch.empty((2, 2, self.B), device=d)
+            self.pmr_stats = torch.zeros(8, device=d)
+            self._pmr_B = self.B
+
+    def _proto_ce(self, m, feat, label, st):
+        """gdl_proto_ce for modality m (0 audio, 1 visual) behind its encoder's training forward, on that encoder's stream"""
+        L.call("gdl_proto_ce", L.ptr(feat), L.ptr(self.prototypes.protos[m]), L.ptr(label), L.ptr(self.pmr_u[m]),
+               L.ptr(self.pmr_terms[m]), None, self.B, self.n_classes, 512, st)
 
     def _uni_operands(self, dv):
         """(wa, wv, ldw, ba, bv): the two modalities' linear maps inside a concat or sum head, for a visual width of dv."""
@@ -1015,4 +1096,7 @@ class DGLTrainer(ArenaTrainer):
         if self._mod is not None and self._mod_now:  # the last step was modulated (the statistics above are the unmodulated ones)
             m = self.mod_stats[:5].cpu().numpy()
             r["ogm"] = dict(score_a=float(m[0]), score_v=float(m[1]), ratio_v=float(m[2]), coeff_a=float(m[3]), coeff_v=float(m[4]))
+        if self._pmr_now:  # the last step carried the prototype term (loss_f above is CE(out) alone)
+            m = self.pmr_stats.cpu().numpy()
+            r["pmr"] = dict(zip(("score_a", "score_v", "rho", "beta", "lam", "lossp_a", "lossp_v"), (float(v) for v in m[:7])))
         return self._read_diversity(r)

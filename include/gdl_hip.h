@@ -770,6 +770,44 @@ GDL_API int gdl_linprobe_epoch(const float* bank, const int64_t* labels, int64_t
                                float* W, float* b, float* mW, float* mb, int n_classes, float lr, float momentum,
                                float weight_decay, float max_norm, double* loss_acc, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ prototypical modal rebalance (PMR) on the joint step
+ * A prototype cross-entropy on each encoder's pooled feature, added to the joint loss for the modality that is behind (Fan et
+ * al., CVPR 2023; DESIGN.md section 8 is this project's statement of the arithmetic).  All tensors float32 on the device, feature
+ * width 512, at most 512 classes.  No launch has a floating-point atomic, no block waits for another, every sum has one order:
+ * two calls on the same inputs give the same bytes.  Nothing is allocated, nothing synchronises, there is no workspace.
+ *
+ * gdl_proto_ce -- one modality: f [B][512] features, P [n][512] prototypes, labels [B] int64.
+ *   d[b][j] = sqrt(sum_k (f[b][k] - P[j][k])^2): per lane the differences of features l, l + 64, .. squared and added as one fmaf
+ *   chain, then the xor butterfly 32 .. 1 (a direct sum, not the |f|^2 - 2 f.P + |P|^2 expansion), one sqrtf;  sim = -d;
+ *   softmax as in gdl_softmax_ce: row max, expf, the exponentials summed in ascending class order, lse = max + logf(sum),
+ *   p = expf(sim - lse);  q[b][j] = ((p[b][j] - [j == label_b]) / B) / d[b][j], 0 where d = 0 (torch's sqrt backward: NaN);
+ *   u[b][k] = sum_j q[b][j] (P[j][k] - f[b][k]), classes ascending, one fmaf chain = d lossp / d f[b][k] of
+ *   lossp = CrossEntropyLoss(sim, labels) (mean over B).
+ *   Writes u [B][512]; terms [2][B]: terms[b] = p[b][label_b], terms[B + b] = lse_b - sim[b][label_b]; and sim [B][n] unless sim
+ *   is NULL.  A label outside [0, n): no one-hot term, terms[b] = 0, terms[B + b] = NaN.
+ *   GDL_ERR_ARG, without a launch: width != 512, n_classes outside [1, 512], B < 1, a NULL pointer other than sim.
+ * gdl_proto_apply -- both modalities, behind the two gdl_proto_ce on a stream that orders them: folds terms_a / terms_v
+ *   ([2][B] each) into score_a, score_v and the two loss sums, each in the order of the loss sums of gdl_softmax_ce (256 partial
+ *   sums p[b & 255] taking b, b + 256, .. in turn, then the tree p[i] += p[i + o], o = 128 .. 1), then
+ *     rho = score_a / score_v;  rho > 1: beta = 0, lam = alpha;  rho < 1: beta = alpha, lam = 0;  otherwise (1 or NaN) both 0
+ *     dfa[b][k] = fmaf(beta, u_a[b][k], dfa[b][k]);  dfv[b][k] = fmaf(lam, u_v[b][k], dfv[b][k])
+ *   A side whose coefficient is 0 is neither read nor written: its df keeps its bits.  stats[8] = {score_a, score_v, rho, beta,
+ *   lam, lossp_a, lossp_v, 0} with lossp = (loss sum) / B.
+ *   GDL_ERR_ARG: width != 512, B outside [1, 2^22], a NULL pointer, u_a / u_v / dfa / dfv not 16-byte aligned.
+ * gdl_proto_update -- one feature bank: bank [N][512], labels [N] int64, P [n][512] updated in place.  Per class c the rows with
+ *   label c are added in ascending row order into float64 accumulators (one block walks the whole bank for its class: the row range
+ *   is not split, so there are no partial sums to combine), mean = sum / count in float64, then
+ *     first != 0: P_c = mean;   first == 0: P_c = (1 - momentum) P_c + momentum mean       (float64, rounded to float32 once)
+ *   A class without a row keeps its prototype (the published script divides by zero there).  count[n] int64 = rows per class;
+ *   info[2] int64 = {classes without a row, rows whose label is outside [0, n): they belong to no class}.
+ *   GDL_ERR_ARG: width != 512, n_classes outside [1, 512], N < 1, momentum outside [0, 1], a NULL pointer. */
+GDL_API int gdl_proto_ce(const float* f, const float* P, const int64_t* labels, float* u, float* terms, float* sim, int B,
+                         int n_classes, int width, void* stream);
+GDL_API int gdl_proto_apply(const float* terms_a, const float* terms_v, const float* u_a, const float* u_v, float* dfa, float* dfv,
+                            float alpha, float* stats, int B, int width, void* stream);
+GDL_API int gdl_proto_update(const float* bank, const int64_t* labels, int64_t N, float* P, int n_classes, int width,
+                             double momentum, int first, int64_t* count, int64_t* info, void* stream);
+
 /* ------------------------------------------------------------------ measurement tap
  * Optional HIP-event timing of every kernel launch (off by default).  While enabled, each
  * launcher records an event pair on the launching stream and its algorithmic work (flops for
