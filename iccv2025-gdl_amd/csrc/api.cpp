@@ -334,6 +334,30 @@ int gdl_proto_update(const float* bank, const int64_t* labels, int64_t N, float*
     GDL_REQUIRE(bank && labels && P && count && info, "proto_update: null argument");
     return proto_update(bank, labels, N, P, n_classes, momentum, first != 0, count, info, (hipStream_t)stream);
 }
+int gdl_mla_feature_mean(const float* h, int B, float* r, void* stream) {
+    GDL_REQUIRE(B >= 1, "mla_feature_mean: B must be at least 1, got %d", B);
+    GDL_REQUIRE(h && r, "mla_feature_mean: null argument");
+    return mla_feature_mean(h, B, r, (hipStream_t)stream);
+}
+size_t gdl_mla_projector_workspace_bytes(void) { return mla_projector_ws_bytes(); }
+int gdl_mla_projector_update(float* P, const float* r, float alpha, int normalize, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(P && r && ws, "mla_projector_update: null argument");
+    GDL_REQUIRE(alpha > 0.f && alpha <= 3.0e38f, "mla_projector_update: alpha must be a finite positive number, got %g", (double)alpha);
+    GDL_REQUIRE(ws_bytes >= mla_projector_ws_bytes(), "mla_projector_update: workspace %zu < %zu", ws_bytes, mla_projector_ws_bytes());
+    GDL_REQUIRE(((uintptr_t)ws & 3) == 0, "mla_projector_update: the workspace must be 4-byte aligned");
+    return mla_projector_update(P, r, alpha, normalize != 0, ws, (hipStream_t)stream);
+}
+int gdl_mla_project(float* dW, const float* P, int n_classes, void* stream) {
+    GDL_REQUIRE(n_classes >= 1 && n_classes <= 512, "mla_project: n_classes must be in [1, 512], got %d", n_classes);
+    GDL_REQUIRE(dW && P, "mla_project: null argument");
+    return mla_project(dW, P, n_classes, (hipStream_t)stream);
+}
+int gdl_mla_fuse(const float* out_a, const float* out_v, int B, int n_classes, int dynamic, float* out, float* lam, void* stream) {
+    GDL_REQUIRE(n_classes >= 1 && n_classes <= 512, "mla_fuse: n_classes must be in [1, 512], got %d", n_classes);
+    GDL_REQUIRE(B >= 1, "mla_fuse: B must be at least 1, got %d", B);
+    GDL_REQUIRE(out_a && out_v && out, "mla_fuse: null argument (only lam may be NULL)");
+    return mla_fuse(out_a, out_v, B, n_classes, dynamic != 0, out, lam, (hipStream_t)stream);
+}
 size_t gdl_feature_diversity_workspace_bytes(int n_img) { return feature_diversity_ws_bytes(n_img); }
 int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int P, int C, float* per_image, float* mean_out,
                           float* accum, void* ws, size_t ws_bytes, void* stream) {

@@ -179,6 +179,12 @@ int proto_apply(const float* terms_a, const float* terms_v, const float* u_a, co
                 float* stats, int B, hipStream_t st);
 int proto_update(const float* bank, const int64_t* labels, int64_t N, float* P, int n, double momentum, int first, int64_t* count,
                  int64_t* info, hipStream_t st);
+// mla.hip: alternating unimodal training on a shared head (the projector of the head's weight gradient, the entropy-weighted fusion)
+int mla_feature_mean(const float* h, int B, float* r, hipStream_t st);
+size_t mla_projector_ws_bytes();
+int mla_projector_update(float* P, const float* r, float alpha, int normalize, void* ws, hipStream_t st);
+int mla_project(float* dW, const float* P, int n, hipStream_t st);
+int mla_fuse(const float* out_a, const float* out_v, int B, int n, int dynamic, float* out, float* lam, hipStream_t st);
 // head_mtl.hip: the one-launch junction of the step whose fused loss reaches the encoders (concat / sum DGL head, un-detached)
 size_t head_mtl_ce_ws_bytes(int B);
 int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,

@@ -15,7 +15,12 @@ def __getattr__(name):
     `gdl.random_wave_starts`, `gdl.AUDIO_STAGES`), and the linear probe of gdl.probe (`gdl.extract_features`, `gdl.FeatureBank`,
     `gdl.LinearProbe`, `gdl.probe_order`, `gdl.multistep_lr`), and `gdl.ScoreBank`, the evaluation report of gdl.evaluate (mAP,
     top-k, confusion), and the class prototypes of gdl.prototypes (`gdl.Prototypes`, `gdl.prototype_logits`: prototypical modal
-    rebalance on the joint step) -- imported on first use (they import torch)."""
+    rebalance on the joint step), and `gdl.MLATrainer` with its schedule helper `gdl.mla_alpha` (gdl.mla: alternating unimodal
+    training on a shared head) -- imported on first use (they import torch)."""
+    if name in ("MLATrainer", "mla_alpha"):
+        from . import mla
+
+        return getattr(mla, name)
     if name in ("Prototypes", "prototype_logits"):
         from . import prototypes
 

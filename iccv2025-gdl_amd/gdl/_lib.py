@@ -114,6 +114,11 @@ SIGNATURES = {
     "gdl_proto_ce": ("i", "pppppp" + "iii" + "p"),
     "gdl_proto_apply": ("i", "pppppp" + "f" + "p" + "ii" + "p"),
     "gdl_proto_update": ("i", "ppl" + "p" + "ii" + "d" + "i" + "pp" + "p"),
+    "gdl_mla_feature_mean": ("i", "pip" + "p"),
+    "gdl_mla_projector_workspace_bytes": ("z", ""),
+    "gdl_mla_projector_update": ("i", "pp" + "fi" + "pz" + "p"),
+    "gdl_mla_project": ("i", "ppi" + "p"),
+    "gdl_mla_fuse": ("i", "pp" + "iii" + "pp" + "p"),
     "gdl_feature_diversity_workspace_bytes": ("z", "i"),
     "gdl_feature_diversity": ("i", "p" + "iiiii" + "ppp" + "pz" + "p"),
     "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),

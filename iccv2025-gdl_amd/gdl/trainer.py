@@ -161,16 +161,7 @@ class ArenaTrainer:
             p.data = v  # the module now aliases the arena: state_dict / eval see the trained weights
             self.pviews.append(v)
             self.gviews.append(self.grads[offs[i]:offs[i + 1]].view(p.shape))
-        h = ctypes.c_void_p()
-        so = (ctypes.c_int64 * len(offs))(*offs)
-        sg = (ctypes.c_int32 * len(group))(*group)
-        L.call("gdl_optim_create", ctypes.byref(h), so, sg, len(group))
-        self.opt = h
-        self.opt_ws_bytes = self.lib.gdl_optim_workspace_bytes(h)
-        self.opt_ws = torch.empty(max(self.opt_ws_bytes, 8), dtype=torch.uint8, device=self.device)
-        # (explicit: a caching allocator may hand out a block at the address of an earlier trainer's workspace)
-        L.call("gdl_optim_bind_workspace", self.opt, L.ptr(self.opt_ws), self.opt_ws_bytes, L.cur_stream())
-        self.stats = torch.zeros(self.lib.gdl_optim_stats_len(h), device=self.device)
+        self._create_descriptors(offs, group)
         # The two chain streams are shared by every trainer of a process on this device: torch hands out a NEW pool stream per
         # torch.cuda.Stream() call and never retires one, and once more distinct streams have carried work than the runtime has
         # hardware queues (four), two chains can end up time-slicing one queue -- the third trainer built in a process ran its step
@@ -192,6 +183,23 @@ class ArenaTrainer:
         self._div_keys = ()
         # the step journal (a subclass calls `_setup_journal`): None = nothing allocated, nothing launched
         self._journal = None
+
+    def _descriptor(self, offs, group):
+        """(descriptor, workspace bytes, workspace, statistics) of the library's optimizer over the segments `offs` (len(group) + 1
+        element offsets from the pointers its calls are given) with the optimizer groups `group`"""
+        h = ctypes.c_void_p()
+        so = (ctypes.c_int64 * len(offs))(*offs)
+        sg = (ctypes.c_int32 * len(group))(*group)
+        L.call("gdl_optim_create", ctypes.byref(h), so, sg, len(group))
+        nb = self.lib.gdl_optim_workspace_bytes(h)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        # (explicit: a caching allocator may hand out a block at the address of an earlier trainer's workspace)
+        L.call("gdl_optim_bind_workspace", h, L.ptr(ws), nb, L.cur_stream())
+        return h, nb, ws, torch.zeros(self.lib.gdl_optim_stats_len(h), device=self.device)
+
+    def _create_descriptors(self, offs, group):
+        """One descriptor over the whole arena; a runner whose steps update sub-ranges of it builds its own instead."""
+        self.opt, self.opt_ws_bytes, self.opt_ws, self.stats = self._descriptor(offs, group)
 
     def _setup_modulation(self, marks, noise, alpha, seed):
         """OGM / OGM-GE over the gradient arena: marks[i] = 0 (untouched), 1 (audio) or 2 (visual) per arena tensor; `noise` =

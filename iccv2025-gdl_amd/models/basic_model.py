@@ -199,3 +199,26 @@ class AVClassifier(nn.Module):
         v = self.visual_net.forward_pooled(visual)
         a, v, out = self.fusion_module(a, v)
         return a, v, out
+
+
+class AVClassifier_MLA(nn.Module):
+    """The model of alternating unimodal training on a shared head (MLA, Zhang et al., CVPR 2024): the two
+    ResNet18 encoders as `AVClassifier_DGL` builds them and ONE `Linear(512, n_classes)` that classifies either modality's pooled
+    feature.  NOT a class of the reference (it has no MLA script): a parameter container over its parts for `gdl.MLATrainer`,
+    registered as audio_net, visual_net, classifier.  forward returns (out, out_a, out_v) with the static fusion out = 0.5 out_a
+    + 0.5 out_v; the entropy-weighted fusion is `MLATrainer.valid(dynamic=True)` / `gdl_mla_fuse`."""
+
+    def __init__(self, args):
+        super(AVClassifier_MLA, self).__init__()
+        if args.dataset not in N_CLASSES:
+            raise NotImplementedError('Incorrect dataset name {}'.format(args.dataset))
+        self.audio_net = resnet18(modality='audio', args=args)
+        self.visual_net = resnet18(modality='visual', args=args)
+        self.classifier = Classifier(512, N_CLASSES[args.dataset])
+        self.modality = 'full'
+        self.args = args
+
+    def forward(self, audio, visual):
+        out_a = self.classifier(self.audio_net.forward_pooled(audio))
+        out_v = self.classifier(self.visual_net.forward_pooled(visual))
+        return 0.5 * out_a + 0.5 * out_v, out_a, out_v

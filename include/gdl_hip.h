@@ -808,6 +808,41 @@ GDL_API int gdl_proto_apply(const float* terms_a, const float* terms_v, const fl
 GDL_API int gdl_proto_update(const float* bank, const int64_t* labels, int64_t N, float* P, int n_classes, int width,
                              double momentum, int first, int64_t* count, int64_t* info, void* stream);
 
+/* ------------------------------------------------------------------ alternating unimodal training on a shared head (MLA)
+ * The device arithmetic of gdl.MLATrainer (Zhang et al., CVPR 2024; DESIGN.md section 8 is this project's statement of the
+ * method): the projector P [512][512] that shapes the shared head's weight gradient, and the entropy-weighted fusion of the two
+ * unimodal logit sets at test time.  All tensors float32 on the device.  No launch has a floating-point atomic, no block waits
+ * for another, every sum has one order that does not depend on the launch geometry: two calls on the same inputs give the same
+ * bytes.  Nothing is allocated, nothing synchronises.  dot512(x, y) below is ONE order: 64 partial sums, partial l taking
+ * x[l + 64 m] y[l + 64 m] for m = 0 .. 7 as one fmaf chain from 0, then the tree s[l] += s[l ^ o], o = 32 .. 1.
+ *
+ * gdl_mla_feature_mean -- r[k] = (sum_b h[b][k]) / B for h [B][512]: plain adds from 0 with b ascending, one division.
+ *   GDL_ERR_ARG: B < 1, a NULL pointer.
+ * gdl_mla_projector_update -- P updated in place against r [512] and the host scalar alpha > 0:
+ *     k[i] = dot512(P[i], r);   c = alpha + dot512(r, k);   P[i][j] = P[i][j] - (k[i] k[j]) / c
+ *   the product rounded first, then one division, then one subtraction, none contracted: a P that is symmetric stays symmetric
+ *   bit for bit.  normalize != 0: P = P / ||P||_F afterwards, with ||P||_F = (float)sqrt(S), S the double sum of the 512 row sums
+ *   dot512(P[i], P[i]) (float) -- partial l taking rows l + 64 m, m ascending, then the same tree -- and one division per entry.
+ *   Two launches, three with normalize (k lives in the workspace between them: no block reads a row another block rewrites).
+ *   ws: gdl_mla_projector_workspace_bytes() bytes, 4-byte aligned, contents irrelevant.
+ *   GDL_ERR_ARG, without a launch: a NULL pointer, alpha not a finite positive number, a workspace too small or misaligned.
+ * gdl_mla_project -- dW [n][512] <- dW P^T in place: new dW[c][i] = dot512(old dW[c], P[i]).  A block owns whole rows of dW and
+ *   has loaded them before it stores.  GDL_ERR_ARG, nothing launched or touched: n_classes outside [1, 512], a NULL pointer.
+ * gdl_mla_fuse -- out_a, out_v [B][n] -> out [B][n] and, unless lam is NULL, lam [B][2] = {lam_a, lam_v}.  Per sample and set:
+ *     lse = max + logf(sum_j expf(l_j - max)), the exponentials added in ascending class order;  p_j = expf(l_j - lse);
+ *     e = sum_j p_j (lse - l_j) in ascending class order (every term >= 0: a p_j of 0 contributes 0);
+ *   w_m = expf(-(e_m - min(e_a, e_v))), lam_m = w_m / (w_a + w_v), out = lam_a out_a + lam_v out_v (two rounded products and one
+ *   add).  Equal entropies give lam = 0.5, 0.5 exactly.  A NaN or inf logit in either set makes both lam and the whole out row
+ *   NaN.  dynamic == 0: lam = 0.5, 0.5, no entropy is computed (a non-finite logit then reaches only its own class of out).
+ *   GDL_ERR_ARG: n_classes outside [1, 512], B < 1, a NULL pointer other than lam. */
+GDL_API int gdl_mla_feature_mean(const float* h, int B, float* r, void* stream);
+GDL_API size_t gdl_mla_projector_workspace_bytes(void);
+GDL_API int gdl_mla_projector_update(float* P, const float* r, float alpha, int normalize, void* ws, size_t ws_bytes,
+                                     void* stream);
+GDL_API int gdl_mla_project(float* dW, const float* P, int n_classes, void* stream);
+GDL_API int gdl_mla_fuse(const float* out_a, const float* out_v, int B, int n_classes, int dynamic, float* out, float* lam,
+                         void* stream);
+
 /* ------------------------------------------------------------------ measurement tap
  * Optional HIP-event timing of every kernel launch (off by default).  While enabled, each
  * launcher records an event pair on the launching stream and its algorithmic work (flops for
