@@ -9,6 +9,7 @@
 // double), one tiny finalise kernel that leaves {total_norm, clip_coef, audio_sum,
 // visual_sum, per-parameter norms} on the device, and one streaming update kernel.
 #include "common.h"
+#include "philox.h"
 #include "prof.h"
 
 #include <string.h>
@@ -290,43 +291,7 @@ __global__ __launch_bounds__(256) void adagrad_kernel(float* __restrict__ p, flo
 // Three launches: the per-chunk sum of the marked chunks (the statistics pass has the sum of squares), one block that turns
 // the scores into the two coefficients and the sums into the per-segment sigma, and the chunked in-place pass.
 
-// Philox4x32-10 (Salmon et al., SC'11): counter c, key k.
-struct Philox4 {
-    uint32_t v[4];
-};
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
-// Box-Muller on a pair of words, u(w) = ((w >> 8) + 0.5) 2^-24: r = sqrt(-2 ln u(wa)), theta = 2 pi u(wb).  (w >> 8) + 0.5 has
-// 25 significant bits, so the radius takes its logarithm in double: a float u rounds to 1 next to it, where ln u is all error.
-__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {
-    const float r = (float)sqrt(-2.0 * log(((double)(wa >> 8) + 0.5) * 0x1p-24));
-    const float th = 6.283185307179586f * (((float)(wb >> 8) + 0.5f) * 0x1p-24f);
-    float sn, cs;
-    sincosf(th, &sn, &cs);
-    z0 = r * cs;
-    z1 = r * sn;
-}
-
-// the four normals of the aligned group of arena elements 4 q .. 4 q + 3 at `step`: element i takes z[i & 3]
-__device__ __forceinline__ void noise4(int64_t q, int64_t step, uint32_t seed_lo, uint32_t seed_hi, float (&z)[4]) {
-    const Philox4 w = philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)step, (uint32_t)((uint64_t)step >> 32),
-                                    seed_lo, seed_hi);
-    box_muller(w.v[0], w.v[1], z[0], z[1]);
-    box_muller(w.v[2], w.v[3], z[2], z[3]);
-}
+// (the generator -- Philox4x32-10, Box-Muller and noise4, the keying by arena element -- is in philox.h)
 
 // sum of g over each chunk of a marked segment (float per thread over at most 32 elements, then double, in a fixed order)
 __global__ __launch_bounds__(256) void mod_sum_kernel(const float* __restrict__ g, const ChunkDesc* __restrict__ chunks,

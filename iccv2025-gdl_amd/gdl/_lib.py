@@ -163,6 +163,11 @@ SIGNATURES = {
     "gdl_optim_modulate_stats_len": ("i", "p"),
     "gdl_optim_modulate_bind": ("i", "pppzp"),
     "gdl_optim_modulate": ("i", "pppfpf" + "ill" + "ppp" + "p"),
+    "gdl_dul_sample_workspace_bytes": ("z", "iii"),
+    "gdl_dul_sample": ("i", "ippppp" + "lli" + "pppppp" + "iiii" + "pz" + "p"),
+    "gdl_dul_bwd_reduce": ("i", "ippppllif" + "pppp" + "iiii" + "p"),
+    "gdl_dul_bwd_apply": ("i", "ippppllif" + "pppppppp" + "iiii" + "p"),
+    "gdl_dul_eval": ("i", "pppppp" + "ii" + "p"),
     "gdl_encoder_create": ("i", "piiiiii"),
     "gdl_encoder_destroy": (None, "p"),
     "gdl_encoder_side_stream": ("i", "pi"),

@@ -81,6 +81,8 @@ class MLATrainer(ArenaTrainer):
         self.shaping, self.normalize = bool(shaping), bool(normalize)
         self.shaping_alpha = shaping_alpha
         self._check_alpha()
+        if getattr(model.audio_net, "pe", False) or getattr(model.visual_net, "pe", False):
+            raise L.GdlError(f"{who}: the probabilistic-embedding branch (args.pe) is not built for alternating unimodal training")
         named = [("audio_net." + n, p) for n, p in model.audio_net.named_parameters()]
         named += [("classifier.weight", cls.weight), ("classifier.bias", cls.bias)]
         named += [("visual_net." + n, p) for n, p in model.visual_net.named_parameters()]

@@ -99,6 +99,8 @@ def _encoder_of(model, modality):
     if hasattr(net, "cfg") and hasattr(net, "num_features"):
         raise L.GdlError(f"extract_features: the Swin branch ({int(net.num_features)} features) is not built for the linear probe "
                          f"(ResNet18 encoders, {FEAT} features)")
+    if getattr(net, "pe", False):
+        raise L.GdlError("extract_features: the probabilistic-embedding branch (args.pe) is not built for the linear probe")
     if not hasattr(net, "_bn_layers") or len(list(net.parameters())) != L.ENC_NPARAMS:
         raise L.GdlError(f"extract_features: {modality}_net must be the ResNet18 mirror (60 tensors)")
     return net

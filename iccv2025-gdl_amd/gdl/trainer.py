@@ -319,12 +319,18 @@ class ArenaTrainer:
         """Optimizer-side state a reference checkpoint keeps besides model.state_dict() (optimizer.state_dict() /
         scheduler, main_dgl.py:372): the optimizer's kind and state arenas, learning rate, step count (which the Adam bias
         corrections count from)."""
-        return {"optimizer": self.optimizer, **{k: v.detach().clone() for k, v in self._opt_state().items()}, "lr": self.lr,
-                "steps": self.steps, "names": list(self.names), "offsets": list(self.offsets), "mu": self.mu,
-                "weight_decay": self.wd}
+        sd = {"optimizer": self.optimizer, **{k: v.detach().clone() for k, v in self._opt_state().items()}, "lr": self.lr,
+              "steps": self.steps, "names": list(self.names), "offsets": list(self.offsets), "mu": self.mu,
+              "weight_decay": self.wd}
+        if getattr(self, "pe", False):  # the probabilistic-embedding branch: `steps` above and this seed key its noise
+            sd.update(pe=True, pe_beta=self.beta, pe_seed=self.seed)
+        return sd
 
     def load_state_dict(self, sd):
         who = type(self).__name__
+        if bool(sd.get("pe", False)) != bool(getattr(self, "pe", False)):
+            raise L.GdlError(f"{who}.load_state_dict: the checkpoint was trained " + ("with" if sd.get("pe", False) else "without") +
+                             " the probabilistic-embedding branch, this trainer runs " + ("without" if sd.get("pe", False) else "with") + " it")
         if list(sd["offsets"]) != list(self.offsets) or list(sd["names"]) != list(self.names):
             raise L.GdlError(f"{who}.load_state_dict: the checkpoint's parameter layout differs from this model's")
         kind = sd.get("optimizer", "sgd")  # (checkpoints written before the optimizer switch are SGD's)
@@ -333,6 +339,8 @@ class ArenaTrainer:
         for k, v in self._opt_state().items():
             v.copy_(sd[k].to(self.device))
         self.lr, self.steps = float(sd["lr"]), int(sd["steps"])
+        if getattr(self, "pe", False):  # the noise continues the checkpoint's stream: its key, and the step count loaded above
+            self.seed = int(sd.get("pe_seed", self.seed))
 
     def close(self):
         """Releases what the trainer owns outside PyTorch's allocator: the optimizer descriptor and, for
@@ -423,7 +431,7 @@ class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
                  modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True,
-                 diversity=False, journal=0, prototypes=None):
+                 diversity=False, journal=0, prototypes=None, beta=0.0):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
@@ -461,11 +469,40 @@ class DGLTrainer(ArenaTrainer):
         gradients, the logits and `loss_f` (= CE(out)) are those of the plain joint step bit for bit.  `read()` gains `pmr` =
         {score_a, score_v, rho, beta, lam, lossp_a, lossp_v}; the journal's columns are unchanged.  The caller refreshes the
         prototypes once per epoch (`prototypes.update`).  Outside the window, or without prototypes, nothing is allocated or
-        launched.  `state_dict()` carries the prototypes' state when they are attached."""
+        launched.  `state_dict()` carries the prototypes' state when they are attached.
+        beta: main.py's --beta for a model built with args.pe (the probabilistic-embedding stacks on both ResNet18 encoders; the
+        switch is the model having them): gdl.dul.DulStage stands behind each encoder's training forward on that encoder's
+        stream and between its feature gradient and its backward, in every form of the step (it is head-independent); the
+        loss gains beta (regurize_a + regurize_v), `read()` gains both terms (`loss_f` stays CE(out)), the 8 tensors per
+        encoder follow its 60 in the arena and its optimizer group, `seed` and the step count key the noise (or
+        `step(..., pe_eps=)` supplies it), valid() uses the pooled eval form.  Refused with the branch: the Swin visual
+        branch, a process group, modulation other than "Normal", prototypes.  Without the stacks nothing is allocated or
+        launched, and a non-zero beta is refused."""
         self._check_optimizer(optimizer)
         self._check_modulation(modulation)
         self._check_journal(journal)
         self._check_prototypes(prototypes, mode, modulation, process_group)
+        from .dul import N_DUL, has_stacks
+
+        self.pe = has_stacks(model.audio_net) or has_stacks(model.visual_net)
+        self.beta = float(beta)
+        if self.pe:  # what the branch is not built for is refused before anything is touched, never ignored
+            if not (has_stacks(model.audio_net) and has_stacks(model.visual_net)):
+                raise L.GdlError("DGLTrainer: the probabilistic-embedding branch needs its stacks on both encoders (ResNet18 built "
+                                 "with args.pe); the Swin visual branch has none")
+            if process_group is not None:
+                raise L.GdlError("DGLTrainer: the probabilistic-embedding branch with a process group is not built")
+            if modulation != "Normal":
+                raise L.GdlError(f"DGLTrainer: the probabilistic-embedding branch with modulation={modulation!r} is not built (OGM's "
+                                 "rule \"4-D tensors\" would catch the new 1x1 weights); modulation must be \"Normal\"")
+            if prototypes is not None:
+                raise L.GdlError("DGLTrainer: the probabilistic-embedding branch with prototypes is not built")
+            if not 0 <= int(seed) < 2 ** 63:
+                raise ValueError("DGLTrainer: seed must be in [0, 2**63)")
+        elif self.beta != 0.0:
+            raise L.GdlError("DGLTrainer: beta weighs the probabilistic-embedding regulariser, and this model has no such stacks "
+                             "(build it with args.pe = 1)")
+        ne = self.ne = 60 + (N_DUL if self.pe else 0)  # arena tensors per ResNet18 encoder
         self.model = model
         self.mode = mode
         self.alpha = float(alpha)
@@ -536,7 +573,7 @@ class DGLTrainer(ArenaTrainer):
         # the visual branch: ResNet18 (60 tensors, 512 features) or the Swin composition of SURVEY row N4
         # (models.basic_model.AVClassifier_DGL_Swin: gdl.swin.SwinEngine, num_features wide)
         self.vis_swin = hasattr(model.visual_net, "cfg") and hasattr(model.visual_net, "num_features")
-        self.nv = len(named) - nf - 60
+        self.nv = len(named) - nf - ne
         self.dv = int(model.visual_net.num_features) if self.vis_swin else 512
         self.prototypes = prototypes
         self._pmr_now = False
@@ -551,7 +588,7 @@ class DGLTrainer(ArenaTrainer):
                 raise L.GdlError(f"DGLTrainer: the prototypes are on {prototypes.device}, the model on {device}")
         if self.vis_swin and (self.head != "concat" or mode != "dgl"):
             raise L.GdlError("DGLTrainer: the Swin visual branch is built for the concat DGL head")
-        if not self.vis_swin and self.nv != 60:
+        if not self.vis_swin and self.nv != ne:
             raise L.GdlError("DGLTrainer: visual_net must be the ResNet18 mirror or the SwinTransformer mirror")
         if self.ablation:
             if mode != "dgl":  # the joint step has one loss and nothing to truncate: never silently ignored
@@ -585,7 +622,7 @@ class DGLTrainer(ArenaTrainer):
                                  "a collective of their own)")
             if not 0 <= self.seed < 2 ** 63:
                 raise ValueError("DGLTrainer: seed must be in [0, 2**63)")
-        group = [0] * nf + [1] * 60 + [2] * self.nv
+        group = [0] * nf + [1] * ne + [2] * self.nv
         super().__init__(named, group, device, optimizer, lr, momentum, weight_decay, max_norm)
         if modulation != "Normal":  # every 4-D tensor (convolution weight) of the two encoders; BatchNorm and the head untouched
             self._setup_modulation([g if p.dim() == 4 else 0 for g, (_, p) in zip(group, named)], modulation == "OGM_GE",
@@ -595,13 +632,13 @@ class DGLTrainer(ArenaTrainer):
         # all-reduce buckets (ranges of the flat gradient arena).  layer4 = the last 15 tensors of an encoder, 8.4 M
         # of its 11.2 M parameters, is final right after the first two blocks of the backward: its own bucket lets
         # three quarters of the exchange overlap the rest of the backward.
-        a0, v0 = nf, nf + 60
+        a0, v0 = nf, nf + ne
         # (Swin: the last stage + final norm -- the tensors whose gradients the backward finishes first, SwinEngine.backward
         # phase 1 -- play layer4's part)
         vsplit = v0 + 45 if not self.vis_swin else \
             v0 + next(i for i, (n, _) in enumerate(named[v0:]) if n.startswith("visual_net.layers.%d." % (model.visual_net.num_layers - 1)))
         self.bucket = {"fusion": (0, offs[nf]),
-                       "audio_l4": (offs[a0 + 45], offs[a0 + 60]), "audio_rest": (offs[a0], offs[a0 + 45]),
+                       "audio_l4": (offs[a0 + 45], offs[a0 + ne]), "audio_rest": (offs[a0], offs[a0 + 45]),
                        "visual_l4": (offs[vsplit], offs[v0 + self.nv]), "visual_rest": (offs[v0], offs[vsplit])}
         if process_group is not None:
             from .ddp import BucketReducer
@@ -617,6 +654,8 @@ class DGLTrainer(ArenaTrainer):
             self._setup_diversity(("a_diversity", "v_diversity"))
         self._setup_journal(journal, self.mode == "dgl")
         self.eng_a = self.eng_v = None
+        self.dul = None  # (audio stage, visual stage) once the batch shape is known
+        self._pe_eps = (None, None)
 
     @staticmethod
     def _check_prototypes(prototypes, mode, modulation, process_group):
@@ -754,6 +793,14 @@ class DGLTrainer(ArenaTrainer):
                 raise L.GdlError("DGLTrainer: gradient modulation handles at most 512 classes")
             self.mod_prob = torch.empty((B, 2), device=d)  # softmax(out_a)[label], softmax(out_v)[label] per sample
         self.B = B
+        if self.pe:
+            from .dul import DulStage
+
+            nf, ne = self.nf, self.ne
+            self.dul = (DulStage(self.model.audio_net, self.eng_a, self.pviews[nf + 60:nf + ne], self.gviews[nf + 60:nf + ne]),
+                        DulStage(self.model.visual_net, self.eng_v, self.pviews[nf + ne + 60:nf + 2 * ne],
+                                 self.gviews[nf + ne + 60:nf + 2 * ne]))
+            self.fa_raw, self.fv_raw = torch.empty((B, 512), device=d), torch.empty((B, 512), device=d)  # valid()
 
     def _bind(self):
         m = self.model
@@ -761,15 +808,31 @@ class DGLTrainer(ArenaTrainer):
             self.eng_v.set_params([p.data for p in m.visual_net.parameters()])
         for eng, net in ((self.eng_a, m.audio_net),) + (() if self.vis_swin else ((self.eng_v, m.visual_net),)):
             bns = net._bn_layers()
-            eng.set_params([p.data for p in net.parameters()], [b.running_mean for b in bns],
+            eng.set_params([p.data for p in net.engine_parameters()], [b.running_mean for b in bns],
                            [b.running_var for b in bns], [b.num_batches_tracked for b in bns])
 
+    def _enc_forward(self, m, x):
+        """Encoder m's (0 audio, 1 visual) training forward into self.fa / self.fv on the current stream -- with the
+        probabilistic-embedding branch: the engine up to its final map, then the stage."""
+        eng, f = (self.eng_a, self.fa) if m == 0 else (self.eng_v, self.fv)
+        if not self.pe:
+            eng.forward(x, True, feat_out=f)
+            return
+        _, fmap = eng.forward(x, True, want_feat=False, want_fmap=True)
+        self.dul[m].forward(fmap, f, self.seed, self.steps, self._pe_eps[m])
+
     # ------------------------------------------------------------------ the step
-    def step(self, spec, image, label):
-        """spec [B,F,T'] float, image [B,3,T,H,W] float, label [B] int64 -- all resident on the device."""
+    def step(self, spec, image, label, pe_eps=None):
+        """spec [B,F,T'] float, image [B,3,T,H,W] float, label [B] int64 -- all resident on the device.
+        pe_eps: with the probabilistic-embedding branch, an optional pair (audio, visual) of caller-supplied float32 noise maps
+        [n_img P, 512] in the engine's row order ([n_img][P], e.g. torch.randn of the NCHW map permuted to NHWC), used bit for
+        bit in place of the generator's; either entry may be None."""
         self._prepare(spec, image)
         self._check_label(label)
         self._bind()
+        if pe_eps is not None and not self.pe:
+            raise L.GdlError("DGLTrainer.step: pe_eps given, but the model has no probabilistic-embedding stacks")
+        self._pe_eps = (None, None) if pe_eps is None else (self.dul[0].check_eps(pe_eps[0]), self.dul[1].check_eps(pe_eps[1]))
         # The head, the losses and the optimizer run on the audio chain's stream rather than on the caller's: one stream
         # (hardware queue) less in play measured +1 % (tools: 9 660 -> 9 760 samples/s).  The caller's stream is ordered
         # before the step and behind it, so the call keeps ordinary stream semantics.
@@ -807,13 +870,13 @@ class DGLTrainer(ArenaTrainer):
         if early:
             wa, wv, ldw, ba, bv = self._uni_operands(self.dv)
             with torch.cuda.stream(self.s_v):
-                self.eng_v.forward(image, True, feat_out=self.fv)
+                self._enc_forward(1, image)
                 self._diversity(self.eng_v, 1)
                 L.call("gdl_head_uni_dfeat_w", L.ptr(self.fv), wv, ldw, bv, L.ptr(label), self.alpha, L.ptr(self.dfv), B, n,
                        self.dv, self.s_v.cuda_stream)
                 ev_v = self.s_v.record_event()
             with torch.cuda.stream(self.s_a):
-                self.eng_a.forward(audio, True, feat_out=self.fa)
+                self._enc_forward(0, audio)
                 self._diversity(self.eng_a, 0)
                 L.call("gdl_head_uni_dfeat", L.ptr(self.fa), wa, ldw, ba, L.ptr(label), self.alpha, L.ptr(self.dfa), B, n,
                        self.s_a.cuda_stream)
@@ -837,12 +900,12 @@ class DGLTrainer(ArenaTrainer):
         if pmr:
             self._pmr_buffers()
         with torch.cuda.stream(self.s_v):
-            self.eng_v.forward(image, True, feat_out=self.fv)
+            self._enc_forward(1, image)
             self._diversity(self.eng_v, 1)
             if pmr:
                 self._proto_ce(1, self.fv, label, self.s_v.cuda_stream)
         with torch.cuda.stream(self.s_a):
-            self.eng_a.forward(audio, True, feat_out=self.fa)
+            self._enc_forward(0, audio)
             self._diversity(self.eng_a, 0)
             if pmr:
                 self._proto_ce(0, self.fa, label, self.s_a.cuda_stream)
@@ -934,7 +997,15 @@ class DGLTrainer(ArenaTrainer):
         audio passes are the shorter ones) -- audio_l4, visual_l4, audio_rest here; `visual_rest` is the caller's to launch (the
         early form puts `fusion` in front of it)."""
         red, nf = self.reducer, self.nf
-        gv, ga = self.gviews[nf + 60:nf + 60 + self.nv], self.gviews[nf:nf + 60]
+        ne = self.ne
+        gv, ga = self.gviews[nf + ne:nf + ne + self.nv], self.gviews[nf:nf + ne]
+        if self.pe:  # the stage between each feature gradient and its engine's backward, on the same chain
+            step = self.steps
+            with torch.cuda.stream(self.s_v):
+                self.eng_v.backward(gv[:60], dfmap=self.dul[1].backward(self.dfv, self.beta, self.seed, step, self._pe_eps[1]))
+            with torch.cuda.stream(self.s_a):
+                self.eng_a.backward(ga[:60], dfmap=self.dul[0].backward(self.dfa, self.beta, self.seed, step, self._pe_eps[0]))
+            return
         if red is None:
             with torch.cuda.stream(self.s_v):
                 self.eng_v.backward(gv, dfeat=self.dfv)
@@ -1074,9 +1145,13 @@ class DGLTrainer(ArenaTrainer):
             self.s_a.wait_event(ev)
             self.s_v.wait_event(ev)
             with torch.cuda.stream(self.s_v):
-                self.eng_v.forward(image, False, feat_out=self.fv)
+                self.eng_v.forward(image, False, feat_out=self.fv_raw if self.pe else self.fv)
+                if self.pe:
+                    self.dul[1].eval(self.fv_raw, self.fv)
             with torch.cuda.stream(self.s_a):
-                self.eng_a.forward(audio, False, feat_out=self.fa)
+                self.eng_a.forward(audio, False, feat_out=self.fa_raw if self.pe else self.fa)
+                if self.pe:
+                    self.dul[0].eval(self.fa_raw, self.fa)
             main.wait_stream(self.s_a)
             main.wait_stream(self.s_v)
             st = main.cuda_stream
@@ -1101,6 +1176,8 @@ class DGLTrainer(ArenaTrainer):
         if self.mode == "dgl":
             r["out_a"] = self.out_a.cpu().numpy()
             r["out_v"] = self.out_v.cpu().numpy()
+        if self.pe:  # main.py's regurize_a / regurize_v of the last step (loss_f above is CE(out) alone)
+            r["regurize_a"], r["regurize_v"] = (float(d.reg.cpu().numpy()[0]) for d in self.dul)
         if self._mod is not None and self._mod_now:  # the last step was modulated (the statistics above are the unmodulated ones)
             m = self.mod_stats[:5].cpu().numpy()
             r["ogm"] = dict(score_a=float(m[0]), score_v=float(m[1]), ratio_v=float(m[2]), coeff_a=float(m[3]), coeff_v=float(m[4]))

@@ -11,10 +11,14 @@ gdl.trainer (the modality's own as the chain, the other one -- idle here -- as t
 The flat arena is [classifier.weight, classifier.bias | the encoder's 60 tensors] with the optimizer groups 0 and 1 (audio)
 or 2 (visual), so `audio_grad_sum` / `visual_grad_sum` are the existing statistics and the absent one reads 0.0.  The
 `fusion_module` the reference still constructs in these modes gets no gradient: it stays outside the arena, untouched.
+A model built with args.pe carries the probabilistic-embedding stacks (main.py --pe 1 --beta b): gdl.dul.DulStage then stands
+between the encoder's final map and `f` in the forward, between the head's `df` and the encoder backward in the backward, its 8
+tensors follow the encoder's 60 in the arena (same optimizer group), and `read()` gains `regurize_a` / `regurize_v`.
 """
 import torch
 
 from . import _lib as L
+from .dul import N_DUL, DulStage, has_stacks
 from .encoder import EncoderEngine
 from .trainer import ArenaTrainer
 
@@ -26,14 +30,18 @@ class UnimodalTrainer(ArenaTrainer):
     _script = "main.py"
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=None, max_norm=40.0, dtype=None, optimizer="sgd",
-                 process_group=None, diversity=False, journal=0):
+                 process_group=None, diversity=False, journal=0, beta=0.0, seed=0):
         """diversity: main.py's feature-diversity monitor (:77-89, :183-184, :356) of this model's one encoder -- True: computed
         right behind the training forward on the chain; `read()` gains `a_diversity` (audio) or `v_diversity` (visual),
         `epoch_diversity()` returns its mean since the last reset.  Off (the default) nothing is allocated or launched.
         journal: the script's per-step log kept on the device, as DGLTrainer's -- the capacity in steps of the ring `tr.journal()`
         hands back with the epoch's means in one host copy.  The script's unimodal model returns `out, out, out`: the one loss
         fills loss_f / loss_a / loss_v and mean |out| both abs_out columns; the absent modality's grad_sum reads 0.0, its
-        diversity column NaN.  0 (the default): nothing is allocated or launched."""
+        diversity column NaN.  0 (the default): nothing is allocated or launched.
+        beta, seed: main.py's --beta and the key of the branch's noise, for a model built with args.pe (the switch is the model
+        having the stacks): the step's loss gains beta * regurize, the noise is a function of (seed, step count, modality,
+        element) alone -- or the map `step(..., pe_eps=)` supplies.  beta = 0 is allowed (regurize is still reported).  Without
+        the stacks nothing is allocated or launched, and a non-zero beta is refused."""
         self._check_optimizer(optimizer)
         self._check_journal(journal)
         if process_group is not None:
@@ -46,6 +54,13 @@ class UnimodalTrainer(ArenaTrainer):
         self.modality = modality
         self.mode = "unimodal"
         net = getattr(model, modality + "_net")
+        self.pe = has_stacks(net)
+        self.beta, self.seed = float(beta), int(seed)
+        if not self.pe and self.beta != 0.0:
+            raise L.GdlError("UnimodalTrainer: beta weighs the probabilistic-embedding regulariser, and this model has no such "
+                             "stacks (build it with args.pe = 1)")
+        if self.pe and not 0 <= self.seed < 2 ** 63:
+            raise ValueError("UnimodalTrainer: seed must be in [0, 2**63)")
         cls = getattr(model, modality + "_classifier")
         device = cls.weight.device
         if device.type != "cuda":
@@ -59,14 +74,15 @@ class UnimodalTrainer(ArenaTrainer):
         self.n_classes = cls.weight.shape[0]
         named = [(modality + "_classifier.weight", cls.weight), (modality + "_classifier.bias", cls.bias)]
         named += [(modality + "_net." + n, p) for n, p in net.named_parameters()]
-        if len(named) != 62:
+        ne = 60 + (N_DUL if self.pe else 0)
+        if len(named) != 2 + ne:
             raise L.GdlError("UnimodalTrainer: the encoder must be the ResNet18 mirror (60 tensors)")
         self.nf = 2
-        group = [0, 0] + [1 if modality == "audio" else 2] * 60
+        group = [0, 0] + [1 if modality == "audio" else 2] * ne
         super().__init__(named, group, device, optimizer, lr, momentum, weight_decay, max_norm)
         self.losses = torch.zeros(1, device=self.device)
         self.chain, self.lane = (self.s_a, self.s_v) if modality == "audio" else (self.s_v, self.s_a)
-        self.eng = None
+        self.eng = self.dul = None
         if diversity:
             self._setup_diversity(("a_diversity" if modality == "audio" else "v_diversity",))
         self._setup_journal(journal, True)
@@ -97,19 +113,28 @@ class UnimodalTrainer(ArenaTrainer):
         self.f, self.df = torch.empty((B, 512), device=d), torch.empty((B, 512), device=d)
         self.out, self.dlogits = torch.empty((B, n), device=d), torch.empty((B, n), device=d)
         self.B = B
+        if self.pe:
+            self.dul = DulStage(self.net, self.eng, self.pviews[62:], self.gviews[62:])
+            self.f_raw = torch.empty((B, 512), device=d)  # valid(): the engine's pooled feature in front of gdl_dul_eval
 
     def _bind(self):
         bns = self.net._bn_layers()
-        self.eng.set_params([p.data for p in self.net.parameters()], [b.running_mean for b in bns],
+        self.eng.set_params([p.data for p in self.net.engine_parameters()], [b.running_mean for b in bns],
                             [b.running_var for b in bns], [b.num_batches_tracked for b in bns])
 
     # ------------------------------------------------------------------ the step
-    def step(self, spec, image, label):
+    def step(self, spec, image, label, pe_eps=None):
         """DGLTrainer.step's argument order: spec [B,F,T'] float, image [B,3,T,H,W] float, label [B] int64, resident on the
-        device; the tensor of the modality the model does not have may be None."""
+        device; the tensor of the modality the model does not have may be None.  pe_eps: DGLTrainer.step's pair (audio map,
+        visual map) of caller-supplied noise for the probabilistic-embedding branch; the absent modality's entry is ignored."""
         x = self._input(spec, image)
         self._prepare(x)
         self._check_label(label)
+        eps = None
+        if pe_eps is not None:
+            if not self.pe:
+                raise L.GdlError("UnimodalTrainer.step: pe_eps given, but the model has no probabilistic-embedding stacks")
+            eps = self.dul.check_eps(pe_eps[0 if self.modality == "audio" else 1])
         self._bind()
         caller = torch.cuda.current_stream(self.device)
         main, lane = self.chain, self.lane
@@ -119,7 +144,11 @@ class UnimodalTrainer(ArenaTrainer):
             label = label.contiguous()
             B, n, st = self.B, self.n_classes, main.cuda_stream
             self._mark(main, "start")
-            self.eng.forward(x, True, feat_out=self.f)
+            if self.pe:
+                _, fmap = self.eng.forward(x, True, want_feat=False, want_fmap=True)
+                self.dul.forward(fmap, self.f, self.seed, self.steps, eps)
+            else:
+                self.eng.forward(x, True, feat_out=self.f)
             self._diversity(self.eng, 0)
             self._mark(main, "fwd_done")
             L.call("gdl_head_cls_ce", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.pviews[1]), L.ptr(label), 1.0,
@@ -132,7 +161,10 @@ class UnimodalTrainer(ArenaTrainer):
                 L.call("gdl_head_cls_bwd", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.dlogits), None, L.ptr(self.gviews[0]),
                        L.ptr(self.gviews[1]), B, n, 512, lane.cuda_stream)
                 ev_cls = lane.record_event()
-            self.eng.backward(self.gviews[2:], dfeat=self.df)
+            if self.pe:
+                self.eng.backward(self.gviews[2:62], dfmap=self.dul.backward(self.df, self.beta, self.seed, self.steps, eps))
+            else:
+                self.eng.backward(self.gviews[2:], dfeat=self.df)
             main.wait_event(ev_cls)
             self._finish_step(main, st)
         caller.wait_stream(main)
@@ -156,7 +188,11 @@ class UnimodalTrainer(ArenaTrainer):
             self._bind()
             label = label.contiguous()
             st = L.cur_stream()
-            self.eng.forward(x, False, feat_out=self.f)
+            if self.pe:
+                self.eng.forward(x, False, feat_out=self.f_raw)
+                self.dul.eval(self.f_raw, self.f)
+            else:
+                self.eng.forward(x, False, feat_out=self.f)
             L.call("gdl_head_cls_fwd", L.ptr(self.f), L.ptr(self.pviews[0]), L.ptr(self.pviews[1]), L.ptr(self.out), self.B, n,
                    512, st)
             L.call("gdl_eval_count", L.ptr(self.out), None, None, L.ptr(label), self.B, n, cnt[0].data_ptr(), cnt[1].data_ptr(),
@@ -174,4 +210,6 @@ class UnimodalTrainer(ArenaTrainer):
         r = self._read_stats((self.eng,))
         loss = float(self.losses.cpu().numpy()[0])
         r.update(loss_f=loss, loss_a=loss, loss_v=loss, out=self.out.cpu().numpy())
+        if self.pe:
+            r["regurize_a" if self.modality == "audio" else "regurize_v"] = float(self.dul.reg.cpu().numpy()[0])
         return self._read_diversity(r)

@@ -124,6 +124,13 @@ class ResNet(nn.Module):
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         for idx, (width, stride) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2))):
             setattr(self, "layer%d" % (idx + 1), self._make_layer(block, width, layers[idx], stride=stride))
+        # main.py's --pe: the probabilistic-embedding stacks behind layer4 (the reference's names and order,
+        # models/swin_transformer.py:574-582); the native runners (gdl/dul.py) are their only forward
+        self.pe = bool(getattr(args, "pe", 0))
+        if self.pe:
+            width = 512 * block.expansion
+            self.mu_dul_backbone = nn.Sequential(nn.Conv2d(width, width, kernel_size=1, stride=1, padding=0), bn(width))
+            self.logvar_dul_backbone = nn.Sequential(nn.Conv2d(width, width, kernel_size=1, stride=1, padding=0), bn(width))
         # constructor-time initialisation (backbone.py:117-127): it consumes the global RNG in module order, which
         # seeded runs of the reference depend on, so it is reproduced call for call even though the DGL script
         # re-initialises everything through utils.weight_init afterwards
@@ -186,12 +193,25 @@ class ResNet(nn.Module):
             self._engines[key] = eng
         return eng
 
+    def engine_parameters(self):
+        """The 60 tensors the engine trains, in its order (everything but the --pe stacks, which are registered last)."""
+        ps = list(self.parameters())
+        return ps[:len(ps) - 8] if self.pe else ps
+
+    def dul_parameters(self):
+        """The 8 tensors of the --pe stacks in registration order: mu conv weight / bias, mu BatchNorm weight / bias, then
+        the logvar stack's four."""
+        return list(self.mu_dul_backbone.parameters()) + list(self.logvar_dul_backbone.parameters())
+
     def _bind(self, eng):
         bns = self._bn_layers()
-        eng.set_params([p.data for p in self.parameters()], [b.running_mean for b in bns],
+        eng.set_params([p.data for p in self.engine_parameters()], [b.running_mean for b in bns],
                        [b.running_var for b in bns], [b.num_batches_tracked for b in bns])
 
     def _run(self, x, want):
+        if self.pe:
+            raise NotImplementedError("gdl: the probabilistic-embedding branch (args.pe) has no autograd forward; train it with "
+                                      "the native runners gdl.UnimodalTrainer / gdl.DGLTrainer (beta=...)")
         x = x.float().contiguous()
         return _ResNetFn.apply(self, x, want, *self.parameters())
 

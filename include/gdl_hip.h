@@ -568,6 +568,64 @@ GDL_API int gdl_optim_modulate(gdl_optim_t* o, float* grads, const float* stats,
                                float alpha, int noise, int64_t seed, int64_t step, float* mod_stats, const void* ws,
                                void* mod_ws, void* stream);
 
+/* ------------------------------------------------------------------ probabilistic-embedding branch (--pe, --beta)
+ * main.py's `--pe 1 --beta b`: behind an encoder's final map x [n_img][P][512] (the last block's output after its ReLU, M = n_img
+ * P rows, row r of sample b = r / (T P)) two stacks Conv2d(512, 512, 1) + BatchNorm2d(512), `mu_dul_backbone` and
+ * `logvar_dul_backbone` (models/swin_transformer.py:574-582; the scripts ran them on the ResNet), the reparameterised sample and
+ * its pool (:643-667, basic_model.py:73-82) and the KL term `regurize` (main.py:92-102), which joins the loss as
+ * beta (reg_a + reg_v) (main.py:191-213).  float32 arithmetic whatever the storage dtype of the maps.
+ *
+ * Training forward.  z_mu = x W_mu^T + b_mu, z_lv = x W_lv^T + b_lv (gdl_conv_fwd_bias), each stack's train-mode BatchNorm over
+ * the M rows (gdl_bn_stats, gdl_bn_finalize_train: biased variance, eps 1e-5, running statistics with momentum 0.1 and the
+ * unbiased variance; the bias is part of the batch mean that reaches running_mean).  A stack's constants travel as
+ * bn = float [4][512] = {scale, shift, save_mean, save_rstd}.  gdl_dul_sample:
+ *     mu = fmaf(z_mu, scale_mu, shift_mu)   lv = fmaf(z_lv, scale_lv, shift_lv)   sd = expf(0.5f lv)   out = fmaf(eps, sd, mu)
+ *     f[b][c] = (sum of out[r][c] over the sample's T P rows) / (T P)
+ *     reg[0]  = (sum over rows and channels of 0.5f (sd^2 + mu^2 - logf(sd^2 + 1e-8f) - 1)) / n_img
+ *   (n_img, not B: `regurize` takes the mean over dim 0 of the [B T, ...] maps).  mu_map / sd_map / eps_map / out_map: optional
+ *   float32 [M][512] copies (NULL in a training step) -- what main.py's model returned as a_mul / a_std.
+ *   One launch; the pool and the KL sum each have one fixed order (dul.hip states them), no floating-point atomic: two launches
+ *   on the same data give the same bits.  `ws`: gdl_dul_sample_workspace_bytes, 256-byte aligned, zeroed ONCE by the caller
+ *   (it holds the ticket counter of ticket.h, handed back at zero), one per stream.
+ * Noise.  eps_in != NULL: the caller's float32 [M][512] map, used bit for bit.  eps_in == NULL: standard normals of the
+ *   modulation's generator (Philox4x32-10, Box-Muller with the radius through a double logarithm) keyed
+ *     counter = (e >> 2, 0x80000000 | modality, step low, step high), key = (seed low, seed high)
+ *   for element e = r 512 + c, which takes normal e & 3 of the Box-Muller pairs of words (0, 1) and (2, 3): a function of
+ *   (seed, step, modality, e) alone.  Word 1 of a modulation counter is below 2^29, so the ranges are disjoint, and audio and
+ *   visual differ in word 1.  The noise is never stored: the backward entries regenerate it from the same arguments.
+ * Backward from the head's df [B][512], k = beta / n_img, g = df[b][c] / (T P):
+ *     d_mu = g + k mu      d_sd = g eps + k (sd - sd / (sd^2 + 1e-8f))      d_lv = d_sd 0.5f sd
+ *   gdl_dul_bwd_reduce -> partial_mu, partial_lv [blocks][512][2] = per-block {sum d, sum d xhat} of each stack, blocks =
+ *   gdl_bn_bwd_blocks(M, 512), xhat = (z - save_mean) save_rstd; gdl_bn_bwd_finalize (count = M) of each -> dgamma, dbeta, coef;
+ *   gdl_dul_bwd_apply -> dz = gamma save_rstd (d - coef0 - xhat coef1) of both stacks, in `dtype`.  Then dx = dz_mu W_mu +
+ *   dz_lv W_lv (gdl_conv_dgrad, the second with the first as its addend) is the gradient w.r.t. the post-ReLU map (it reaches
+ *   the engine as gdl_encoder_backward's dfmap_nchw, through gdl_nhwc_to_nchw_f32), dW = dz^T x
+ *   (gdl_conv_wgrad), and db_conv = 0 exactly -- a named departure: a bias in front of a train-mode BatchNorm has a
+ *   mathematically zero gradient, torch leaves the rounding noise of sum dz there.
+ *   beta = 0 is allowed (k = 0: the KL terms vanish from the gradient, reg is still reported).  Non-finite values propagate
+ *   as torch's do (a huge lv gives sd = inf).
+ * Eval.  out = mu with running statistics, then the pool; pooling commutes with a 1x1 convolution and a per-channel affine, so
+ *   gdl_dul_eval: out[b][k] = fmaf(dot(w_mu[k], f[b]) + b_mu[k], scale[k], shift[k]) on the engine's pooled f [B][512], w_mu
+ *   float32 [512][512], scale / shift from gdl_bn_finalize_eval; each dot product in one fixed order; out must not alias f.
+ *   The logvar stack is not evaluated.  A named departure from the literal order (convolve every position, then pool), exact
+ *   in real arithmetic.
+ * All entries: C must be 512, n_img a multiple of T, P, T, n_img >= 1, n_img P < 2^25; maps, bn, coef, df and partials 16-byte
+ * aligned (gamma_*, w_mu, b_mu -- views of a parameter arena -- 4-byte); GDL_ERR_ARG with a message and no launch otherwise. */
+GDL_API size_t gdl_dul_sample_workspace_bytes(int dtype, int n_img, int T);
+GDL_API int gdl_dul_sample(int dtype, const void* z_mu, const void* z_lv, const float* bn_mu, const float* bn_lv,
+                           const float* eps_in, int64_t seed, int64_t step, int modality, float* f, float* reg, float* mu_map,
+                           float* sd_map, float* eps_map, float* out_map, int n_img, int T, int P, int C, void* ws,
+                           size_t ws_bytes, void* stream);
+GDL_API int gdl_dul_bwd_reduce(int dtype, const void* z_mu, const void* z_lv, const float* df, const float* eps_in, int64_t seed,
+                               int64_t step, int modality, float beta, const float* bn_mu, const float* bn_lv, float* partial_mu,
+                               float* partial_lv, int n_img, int T, int P, int C, void* stream);
+GDL_API int gdl_dul_bwd_apply(int dtype, const void* z_mu, const void* z_lv, const float* df, const float* eps_in, int64_t seed,
+                              int64_t step, int modality, float beta, const float* bn_mu, const float* bn_lv,
+                              const float* gamma_mu, const float* gamma_lv, const float* coef_mu, const float* coef_lv, void* dz_mu,
+                              void* dz_lv, int n_img, int T, int P, int C, void* stream);
+GDL_API int gdl_dul_eval(const float* f, const float* w_mu, const float* b_mu, const float* scale, const float* shift, float* out,
+                         int B, int C, void* stream);
+
 /* ------------------------------------------------------------------ ResNet18 encoder engine
  * `resnet18(modality, args)` / ResNet.forward (backbone.py:75-201, 255-257) plus the
  * pooling glue of AVClassifier_DGL.forward (basic_model.py:73-82), as one planned
