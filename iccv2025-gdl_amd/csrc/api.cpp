@@ -358,6 +358,15 @@ int gdl_mla_fuse(const float* out_a, const float* out_v, int B, int n_classes, i
     GDL_REQUIRE(out_a && out_v && out, "mla_fuse: null argument (only lam may be NULL)");
     return mla_fuse(out_a, out_v, B, n_classes, dynamic != 0, out, lam, (hipStream_t)stream);
 }
+size_t gdl_pareto_workspace_bytes(int64_t n) { return pareto_ws_bytes(n); }
+int gdl_pareto_integrate(float* g_m, const float* g_u, int64_t n, float scale, float* info, void* ws, size_t ws_bytes, void* stream) {
+    GDL_REQUIRE(n >= 1 && n <= ((int64_t)1 << 36), "pareto_integrate: n must be in [1, 2^36], got %lld", (long long)n);
+    GDL_REQUIRE(g_m && g_u && info && ws, "pareto_integrate: null argument");
+    GDL_REQUIRE((((uintptr_t)g_m | (uintptr_t)g_u | (uintptr_t)info) & 3) == 0, "pareto_integrate: g_m, g_u and info must be 4-byte aligned");
+    GDL_REQUIRE(((uintptr_t)ws & 15) == 0, "pareto_integrate: the workspace must be 16-byte aligned");
+    GDL_REQUIRE(ws_bytes >= pareto_ws_bytes(n), "pareto_integrate: workspace %zu < %zu", ws_bytes, pareto_ws_bytes(n));
+    return pareto_integrate(g_m, g_u, n, scale, info, ws, (hipStream_t)stream);
+}
 size_t gdl_feature_diversity_workspace_bytes(int n_img) { return feature_diversity_ws_bytes(n_img); }
 int gdl_feature_diversity(const void* map, int dtype, int layout, int n_img, int P, int C, float* per_image, float* mean_out,
                           float* accum, void* ws, size_t ws_bytes, void* stream) {

@@ -185,6 +185,9 @@ size_t mla_projector_ws_bytes();
 int mla_projector_update(float* P, const float* r, float alpha, int normalize, void* ws, hipStream_t st);
 int mla_project(float* dW, const float* P, int n, hipStream_t st);
 int mla_fuse(const float* out_a, const float* out_v, int B, int n, int dynamic, float* out, float* lam, hipStream_t st);
+// pareto.hip: MMPareto integration of one encoder's fused-loss and unimodal-loss gradients (three double dot products, the combine)
+size_t pareto_ws_bytes(int64_t n);
+int pareto_integrate(float* g_m, const float* g_u, int64_t n, float scale, float* info, void* ws, hipStream_t st);
 // head_mtl.hip: the one-launch junction of the step whose fused loss reaches the encoders (concat / sum DGL head, un-detached)
 size_t head_mtl_ce_ws_bytes(int B);
 int head_mtl_ce(const float* fa, const float* fv, const float* Wa, const float* Wv, int ldw, const float* ba, const float* bv,

@@ -119,6 +119,8 @@ SIGNATURES = {
     "gdl_mla_projector_update": ("i", "pp" + "fi" + "pz" + "p"),
     "gdl_mla_project": ("i", "ppi" + "p"),
     "gdl_mla_fuse": ("i", "pp" + "iii" + "pp" + "p"),
+    "gdl_pareto_workspace_bytes": ("z", "l"),
+    "gdl_pareto_integrate": ("i", "pp" + "lf" + "p" + "pz" + "p"),
     "gdl_feature_diversity_workspace_bytes": ("z", "i"),
     "gdl_feature_diversity": ("i", "p" + "iiiii" + "ppp" + "pz" + "p"),
     "gdl_encoder_feature_diversity": ("i", "p" + "ppp" + "pz" + "p"),

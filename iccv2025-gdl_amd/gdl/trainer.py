@@ -37,6 +37,11 @@ needs both encoders' features, so the step is the junction form with ONE launch 
 and the head's parameter gradients behind the junction on the audio stream.  Both off = the multi-task baseline
 loss_f + gamma (loss_a + loss_v) of main.py:177 under plain autograd (alpha = the scripts' --gamma).
 
+MMPareto integration on the multi-task step (`pareto=True`): the junction computes the unimodal losses' feature
+gradients (gdl_head_mtl_ce with fused_reaches = 0) and the fused loss' (one gdl_head_*_bwd from g_f) separately; each encoder's
+stream then carries two backwards of its one forward -- into the gradient arena and into a second arena -- and
+gdl_pareto_integrate, which leaves the integrated gradient in the arena.  The tail is the same.
+
 ArenaTrainer below is what such a runner is before it knows its model (the flat arenas, the optimizer state and its checkpoint,
 the chain streams, the statistics + clip + update tail); DGLTrainer is the step above on it, gdl.unimodal.UnimodalTrainer the
 one-encoder step.
@@ -431,7 +436,7 @@ class DGLTrainer(ArenaTrainer):
     def __init__(self, model, lr, alpha=4.0, momentum=0.9, weight_decay=None, max_norm=40.0, mode="dgl", dtype=None,
                  process_group=None, comm_backend="torch", visual_side_stream=None, early_backward=None, optimizer="sgd",
                  modulation="Normal", modulation_starts=0, modulation_ends=50, seed=0, detach_fused=True, drop_head_uni=True,
-                 diversity=False, journal=0, prototypes=None, beta=0.0):
+                 diversity=False, journal=0, prototypes=None, beta=0.0, pareto=False, pareto_scale=1.0):
         """comm_backend: "torch" -- torch.distributed all_reduce on `process_group` (nccl = RCCL); "abi" -- the library's own
         RCCL communicator (gdl_comm_*), bootstrapped through `process_group`.
         optimizer: main_dgl.py's `args.optimizer` -- "sgd" (momentum, weight decay), "Adam" (AdamW) or "AdaGrad"; weight_decay
@@ -477,14 +482,32 @@ class DGLTrainer(ArenaTrainer):
         encoder follow its 60 in the arena and its optimizer group, `seed` and the step count key the noise (or
         `step(..., pe_eps=)` supplies it), valid() uses the pooled eval form.  Refused with the branch: the Swin visual
         branch, a process group, modulation other than "Normal", prototypes.  Without the stacks nothing is allocated or
-        launched, and a non-zero beta is refused."""
+        launched, and a non-zero beta is refused.
+        pareto, pareto_scale: MMPareto gradient integration (ICML 2024) on the multi-task step -- mode="dgl",
+        detach_fused=False, drop_head_uni=False, the concat or sum head, ResNet18 encoders, at most 512 classes; everything else
+        is refused.  Per encoder the step takes two backwards of its one training forward -- from df_m = g_f W_e (the fused
+        loss) into the gradient arena and from df_u = g_e W_e (alpha times its own unimodal loss) into a second, trainer-owned
+        arena [audio | visual] -- and gdl_pareto_integrate over the encoder's 60 tensors as one vector, all on that encoder's
+        stream: where the two gradients agree (their dot product is positive) the arena receives the min-norm combination
+        rescaled to the norm of the plain sum, elsewhere the plain sum, times `pareto_scale`.  The head keeps the plain
+        multi-task gradient; the clip and the update follow on the integrated arena.  No value is read back; `read()` gains
+        `pareto` = {"audio": {S_mm, S_uu, S_mu, gamma, w_m, w_u, s, branch}, "visual": {...}}.  The logits, the losses and the
+        BatchNorm buffers of a step are those of the plain multi-task step bit for bit.  `state_dict()` records the switch and the
+        scale; a checkpoint of another switch or scale is refused.  Off
+        (the default) nothing is allocated, launched or changed."""
         self._check_optimizer(optimizer)
         self._check_modulation(modulation)
         self._check_journal(journal)
+        self.pareto, self.pareto_scale = bool(pareto), float(pareto_scale)
+        if self.pareto:
+            self._check_pareto(mode, detach_fused, drop_head_uni, process_group, prototypes, modulation, beta, self.pareto_scale)
         self._check_prototypes(prototypes, mode, modulation, process_group)
         from .dul import N_DUL, has_stacks
 
         self.pe = has_stacks(model.audio_net) or has_stacks(model.visual_net)
+        if self.pareto and self.pe:
+            raise L.GdlError("DGLTrainer: pareto=True beside the probabilistic-embedding branch (a model built with args.pe) is not "
+                             "built")
         self.beta = float(beta)
         if self.pe:  # what the branch is not built for is refused before anything is touched, never ignored
             if not (has_stacks(model.audio_net) and has_stacks(model.visual_net)):
@@ -586,6 +609,14 @@ class DGLTrainer(ArenaTrainer):
                 raise L.GdlError(f"DGLTrainer: the prototypes hold {prototypes.n_classes} classes, the model's head {self.n_classes}")
             if prototypes.device != device:
                 raise L.GdlError(f"DGLTrainer: the prototypes are on {prototypes.device}, the model on {device}")
+        if self.pareto:  # (what depends on the model; the switches were checked before it was touched)
+            if self.vis_swin:
+                raise L.GdlError("DGLTrainer: pareto=True is not built for the Swin visual branch (ResNet18 encoders only)")
+            if self.head not in ("concat", "sum"):
+                raise L.GdlError(f"DGLTrainer: pareto=True is built for the concat and sum heads, not for {self.head!r} (its fused "
+                                 "path into the features needs kernels of its own)")
+            if self.n_classes > 512:
+                raise L.GdlError(f"DGLTrainer: pareto=True handles at most 512 classes (gdl_head_mtl_ce), the head has {self.n_classes}")
         if self.vis_swin and (self.head != "concat" or mode != "dgl"):
             raise L.GdlError("DGLTrainer: the Swin visual branch is built for the concat DGL head")
         if not self.vis_swin and self.nv != ne:
@@ -650,6 +681,17 @@ class DGLTrainer(ArenaTrainer):
             # gated head's fc_x / fc_y) live outside the arena: they are never updated but still part of the state.
             self.reducer.sync_state([self.params] + list(self._opt_state().values()) + self._replica_buffers())
         self.losses = torch.zeros(3, device=self.device)  # loss_f, loss_a, loss_v
+        if self.pareto:
+            # the second gradient arena [audio | visual] (the unimodal losses' gradients, laid out like the encoders' part of the
+            # first), an info row and a workspace per encoder
+            e0, e1, e2 = offs[nf], offs[nf + ne], offs[nf + 2 * ne]
+            self.pareto_grads = torch.zeros(e2 - e0, device=self.device)
+            self.pareto_gviews = [self.pareto_grads[offs[i] - e0:offs[i + 1] - e0].view(named[i][1].shape)
+                                  for i in range(nf, nf + 2 * ne)]
+            self.pareto_range = ((e0, e1 - e0), (e1, e2 - e1))  # (offset in the gradient arena, elements) per encoder
+            self.pareto_info = torch.zeros((2, 8), device=self.device)
+            self.pareto_ws = [torch.empty(self.lib.gdl_pareto_workspace_bytes(n_), dtype=torch.uint8, device=self.device)
+                              for _, n_ in self.pareto_range]
         if diversity:
             self._setup_diversity(("a_diversity", "v_diversity"))
         self._setup_journal(journal, self.mode == "dgl")
@@ -676,6 +718,31 @@ class DGLTrainer(ArenaTrainer):
         if process_group is not None:
             raise L.GdlError("DGLTrainer: prototypes with a process group are not supported (the scores are sums over the global "
                              "batch and would need a collective of their own)")
+
+    @staticmethod
+    def _check_pareto(mode, detach_fused, drop_head_uni, process_group, prototypes, modulation, beta, scale):
+        """(like `_check_optimizer`: before the model is touched) MMPareto integration is built for ONE step, the multi-task one;
+        every other configuration is refused with its reason, never ignored.  The checks against the model -- the head, the Swin
+        branch, the probabilistic-embedding stacks, the class count -- follow once it is known."""
+        if mode != "dgl":
+            raise L.GdlError(f"DGLTrainer: pareto=True integrates the fused and the unimodal gradients of the multi-task step "
+                             f"(mode=\"dgl\", detach_fused=False, drop_head_uni=False); the {mode!r} step has one loss")
+        if detach_fused or drop_head_uni:
+            raise L.GdlError("DGLTrainer: pareto=True needs both DGL truncations lifted (detach_fused=False, drop_head_uni=False): "
+                             f"got detach_fused={bool(detach_fused)}, drop_head_uni={bool(drop_head_uni)} -- with the fused logits "
+                             "detached no fused gradient reaches the encoders")
+        if process_group is not None:
+            raise L.GdlError("DGLTrainer: pareto=True with a process group is not built (the three sums would need a collective of "
+                             "their own)")
+        if beta != 0.0:
+            raise L.GdlError("DGLTrainer: pareto=True with beta (the probabilistic-embedding regulariser) is not built")
+        if prototypes is not None:
+            raise L.GdlError("DGLTrainer: pareto=True with prototypes is not built (two rebalancing methods in one step)")
+        if modulation != "Normal":
+            raise L.GdlError(f"DGLTrainer: pareto=True with modulation={modulation!r} is not built (two rebalancing methods in one "
+                             "step); modulation must be \"Normal\"")
+        if not (scale == scale and abs(scale) != float("inf")):
+            raise ValueError(f"DGLTrainer: pareto_scale must be a finite number, got {scale!r}")
 
     def _journal_logits(self):
         return (self.out_a, self.out_v) if self.mode == "dgl" else (None, None)
@@ -705,6 +772,8 @@ class DGLTrainer(ArenaTrainer):
             sd.update(detach_fused=self.detach_fused, drop_head_uni=self.drop_head_uni)
         if self.prototypes is not None:  # (the step's loss depends on them; they carry an epoch-to-epoch momentum)
             sd["prototypes"] = self.prototypes.state_dict()
+        if self.pareto:  # (the encoders' gradient depends on it)
+            sd.update(pareto=True, pareto_scale=self.pareto_scale)
         return sd
 
     def load_state_dict(self, sd):
@@ -716,6 +785,12 @@ class DGLTrainer(ArenaTrainer):
         if sw != (self.detach_fused, self.drop_head_uni):
             raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint was trained with detach_fused={sw[0]}, drop_head_uni={sw[1]}, "
                              f"this trainer runs detach_fused={self.detach_fused}, drop_head_uni={self.drop_head_uni}")
+        if bool(sd.get("pareto", False)) != self.pareto:
+            raise L.GdlError("DGLTrainer.load_state_dict: the checkpoint was trained " + ("with" if sd.get("pareto", False) else "without") +
+                             " pareto integration, this trainer runs " + ("without" if sd.get("pareto", False) else "with") + " it")
+        if self.pareto and float(sd.get("pareto_scale", 1.0)) != self.pareto_scale:  # (it scales the encoders' gradient)
+            raise L.GdlError(f"DGLTrainer.load_state_dict: the checkpoint was trained with pareto_scale={float(sd.get('pareto_scale', 1.0))!r}, "
+                             f"this trainer runs pareto_scale={self.pareto_scale!r}")
         if ("prototypes" in sd) != (self.prototypes is not None):
             raise L.GdlError("DGLTrainer.load_state_dict: the checkpoint was trained " + ("with" if "prototypes" in sd else "without") +
                              " prototypes, this trainer runs " + ("without" if "prototypes" in sd else "with") + " them")
@@ -788,6 +863,8 @@ class DGLTrainer(ArenaTrainer):
         self.g_f, self.g_a, self.g_v = (torch.empty((B, n), device=d) for _ in range(3))
         if not self.detach_fused:  # gdl_head_mtl_ce's ticket counter and loss terms: zeroed here once, left zero by every launch
             self.mtl_ws = torch.zeros(self.lib.gdl_head_mtl_ce_workspace_bytes(B), dtype=torch.uint8, device=d)
+        if self.pareto:  # df_m = g_f W_e, the fused loss' feature gradients (self.dfa / self.dfv hold df_u)
+            self.dfm_a, self.dfm_v = torch.empty((B, 512), device=d), torch.empty((B, 512), device=d)
         if self._mod is not None:
             if n > 512:
                 raise L.GdlError("DGLTrainer: gradient modulation handles at most 512 classes")
@@ -914,14 +991,23 @@ class DGLTrainer(ArenaTrainer):
         self._mark(main, "fwd_done")
         st = main.cuda_stream
         if dgl and not self.detach_fused:
-            self._mtl_junction(label, st)
+            if self.pareto:
+                # the unimodal losses' feature gradients alone (fused_reaches = 0: self.dfa / self.dfv = df_u), then the fused
+                # loss' through the head, df_m = g_f W_e, into buffers of their own
+                self._mtl_junction(label, st, fused_reaches=0)
+                self._fused_dfeat(st)
+            else:
+                self._mtl_junction(label, st)
             self._mark(main, "head_done")
             ev2 = main.record_event()
             self.s_v.wait_event(ev2)
             # the head's parameter gradients behind the junction event, on this stream (= the audio chain, the shorter one) in
             # front of the audio backward, as in the joint step
             self._dgl_head_backward(None, None, st)
-            self._encoders_backward()
+            if self.pareto:
+                self._pareto_backward()
+            else:
+                self._encoders_backward()
             self._finish_step(main, st)
             return
         self._head_forward(dgl, st)
@@ -1024,15 +1110,48 @@ class DGLTrainer(ArenaTrainer):
             self.eng_a.backward(ga, phase=2)
             red.launch("audio_rest")
 
-    def _mtl_junction(self, label, st):
+    def _fused_dfeat(self, st):
+        """(pareto) df_m = g_f W_e for both encoders into self.dfm_a / self.dfm_v: the head's backward from g_f alone, feature
+        gradients only -- the call the joint step makes for its dfa / dfv."""
+        pv, B, n = self.pviews, self.B, self.n_classes
+        if self.head == "sum":
+            L.call("gdl_head_sum_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), L.ptr(pv[2]), None, None, L.ptr(self.g_f),
+                   1, 0, L.ptr(self.dfm_a), L.ptr(self.dfm_v), None, None, None, None, B, n, st)
+        else:
+            L.call("gdl_head_concat_bwd", L.ptr(self.fa), L.ptr(self.fv), L.ptr(pv[0]), None, None, L.ptr(self.g_f), 1, 0,
+                   L.ptr(self.dfm_a), L.ptr(self.dfm_v), None, None, B, n, st)
+
+    def _pareto_backward(self):
+        """(pareto) On each encoder's own stream, the visual one (the critical path) enqueued first: the backward of its training
+        forward from df_m into the gradient arena's views, the same backward from df_u into the second arena, and
+        gdl_pareto_integrate over the encoder's range -- the arena then holds the integrated gradient.  Nothing is read back."""
+        nf, ne = self.nf, self.ne
+        gm = (self.gviews[nf:nf + ne], self.gviews[nf + ne:nf + 2 * ne])
+        gu = (self.pareto_gviews[:ne], self.pareto_gviews[ne:])
+        lanes = ((1, self.s_v, self.eng_v, self.dfm_v, self.dfv), (0, self.s_a, self.eng_a, self.dfm_a, self.dfa))
+        for m, s, eng, dfm, _ in lanes:  # (host order: both first backwards are enqueued before either second one)
+            with torch.cuda.stream(s):
+                eng.backward(gm[m], dfeat=dfm)
+        e0 = self.pareto_range[0][0]
+        for m, s, eng, _, dfu in lanes:
+            off, cnt = self.pareto_range[m]
+            with torch.cuda.stream(s):
+                eng.backward(gu[m], dfeat=dfu)
+                L.call("gdl_pareto_integrate", self.grads.data_ptr() + 4 * off, self.pareto_grads.data_ptr() + 4 * (off - e0), cnt,
+                       self.pareto_scale, L.ptr(self.pareto_info[m]), L.ptr(self.pareto_ws[m]), self.pareto_ws[m].numel(),
+                       s.cuda_stream)
+
+    def _mtl_junction(self, label, st, fused_reaches=1):
         """What stands between the forwards and the backward chains when the fused loss reaches the encoders (concat / sum head):
         the three logit sets, the three losses, their logit gradients and dfa / dfv -- gdl_head_mtl_ce, ONE launch; beyond its 512
-        classes (or with the tuning aid GDL_MTL_FUSED=0) the three launches it replaces, bit for bit."""
+        classes (or with the tuning aid GDL_MTL_FUSED=0) the three launches it replaces, bit for bit.  fused_reaches=0 (the
+        pareto step, at most 512 classes, always the one launch): dfa / dfv carry the unimodal losses' part alone."""
         B, n = self.B, self.n_classes
-        if self.mtl_fused and n <= 512:
+        if (self.mtl_fused or not fused_reaches) and n <= 512:
             wa, wv, ldw, ba, bv = self._uni_operands(512)
             sb = 0 if self.head == "concat" else 1  # `out` carries one bias / bx + by
-            L.call("gdl_head_mtl_ce", L.ptr(self.fa), L.ptr(self.fv), wa, wv, ldw, ba, bv, sb, L.ptr(label), self.alpha, 1,
+            L.call("gdl_head_mtl_ce", L.ptr(self.fa), L.ptr(self.fv), wa, wv, ldw, ba, bv, sb, L.ptr(label), self.alpha,
+                   int(fused_reaches),
                    L.ptr(self.out), L.ptr(self.out_a), L.ptr(self.out_v), self.losses.data_ptr(), L.ptr(self.g_f), L.ptr(self.g_a),
                    L.ptr(self.g_v), L.ptr(self.dfa), L.ptr(self.dfv), B, n, L.ptr(self.mtl_ws), self.mtl_ws.numel(), st)
             return
@@ -1184,4 +1303,9 @@ class DGLTrainer(ArenaTrainer):
         if self._pmr_now:  # the last step carried the prototype term (loss_f above is CE(out) alone)
             m = self.pmr_stats.cpu().numpy()
             r["pmr"] = dict(zip(("score_a", "score_v", "rho", "beta", "lam", "lossp_a", "lossp_v"), (float(v) for v in m[:7])))
+        if self.pareto:  # the last step's integration per encoder: the three sums (as float), the coefficients, the branch
+            keys = ("S_mm", "S_uu", "S_mu", "gamma", "w_m", "w_u", "s", "branch")
+            info = self.pareto_info.cpu().numpy()
+            r["pareto"] = {k: {**{q: float(v) for q, v in zip(keys[:7], row[:7])}, "branch": int(row[7])}
+                           for k, row in zip(("audio", "visual"), info)}
         return self._read_diversity(r)

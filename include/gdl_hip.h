@@ -671,7 +671,10 @@ GDL_API int gdl_encoder_set_params(gdl_encoder_t* e, const float* const* params,
 GDL_API int gdl_encoder_forward(gdl_encoder_t* e, const float* x, int training, float* feat_out, float* fmap_nchw,
                                 void* stream);
 /* backward of the last training forward.  Exactly one of dfeat ([B][512]) / dfmap_nchw
- * is non-NULL.  grads: 60 device pointers (float32, reference layouts), overwritten. */
+ * is non-NULL.  grads: 60 device pointers (float32, reference layouts), overwritten.
+ * The call may be repeated for one forward, with another upstream gradient and other `grads`: it reads the activations the
+ * forward kept and writes only the engine's gradient scratch and `grads`, so every call returns what the first call after that
+ * forward would have returned for its arguments (DGLTrainer's pareto step: two backwards of one forward, in stream order). */
 GDL_API int gdl_encoder_backward(gdl_encoder_t* e, const float* dfeat, const float* dfmap_nchw, float* const* grads,
                                  void* stream);
 /* The same backward in two calls, for data-parallel callers: phase 1 = the upstream gradient and layer4 -- when it
@@ -900,6 +903,35 @@ GDL_API int gdl_mla_projector_update(float* P, const float* r, float alpha, int 
 GDL_API int gdl_mla_project(float* dW, const float* P, int n_classes, void* stream);
 GDL_API int gdl_mla_fuse(const float* out_a, const float* out_v, int B, int n_classes, int dynamic, float* out, float* lam,
                          void* stream);
+
+/* ------------------------------------------------------------------ MMPareto gradient integration on the multi-task step
+ * One encoder's gradient of the fused loss, g_m, and of its own (weighted) unimodal loss, g_u -- n float32 each, the encoder's
+ * tensors as ONE vector -- become one gradient, written over g_m (Wei & Hu, ICML 2024; DESIGN.md section 8 is this project's
+ * statement of the arithmetic).  Where the two agree the result is the min-norm point of the segment [g_u, g_m], rescaled to the
+ * norm of the plain sum; where they conflict it is the plain sum.  g_m, g_u and info need 4-byte alignment only (ranges of a
+ * flat gradient arena).  ONE call = two launches on `stream`, nothing is allocated, nothing synchronises, no device value is
+ * read back:
+ *   1. S_mm = sum g_m^2, S_uu = sum g_u^2, S_mu = sum g_m g_u: every product formed in double, the sums kept in double and added
+ *      in ONE order that depends on n alone -- blocks of 8192 elements, within a block 256 sums (sum t takes the elements
+ *      4 (t + 256 k) .. + 3, k = 0 .. 7, in ascending order) folded by the tree p[i] += p[i + o], o = 128 .. 1; then the blocks'
+ *      sums, sum t taking blocks t, t + 256, .., and the same tree.  No floating-point atomic, no block waits for another; the grid,
+ *      the stream and the alignment of the pointers do not enter: the same values give the same bytes wherever they lie.
+ *   2. by every block of the second launch, from those sums, in double:
+ *        S_mu > 0 and all three sums finite ("agreement", branch 1):
+ *            D = S_mm - 2 S_mu + S_uu;   gamma = D > 0 ? clamp((S_uu - S_mu) / D, 0, 1) : 0.5;   w_m = 2 gamma, w_u = 2 (1 - gamma)
+ *            N_h^2 = w_m^2 S_mm + 2 w_m w_u S_mu + w_u^2 S_uu;   N_s^2 = S_mm + 2 S_mu + S_uu
+ *            s = N_h^2 > 0 and finite ? sqrt(N_s^2 / N_h^2) : 1                                   (>= 1 up to rounding)
+ *        otherwise ("sum", branch 0):  gamma = 0.5, w_m = w_u = 1, s = 1
+ *        c_m = (float)(scale s w_m),  c_u = (float)(scale s w_u);    g_m[i] = fmaf(c_u, g_u[i], c_m * g_m[i])  (the product rounded)
+ *      A NaN or inf anywhere in g_m or g_u therefore gives the plain sum scaled by `scale`, with the NaN where it was.
+ * info[8] (device) = {S_mm, S_uu, S_mu (rounded to float), gamma, w_m, w_u, s, branch}.  ws: gdl_pareto_workspace_bytes(n) bytes,
+ * 16-byte aligned, contents irrelevant before the call; behind it its first two floats are {c_m, c_u} as the combine used them.
+ * g_u is not written.  Calls sharing one `ws` must be ordered on one stream.
+ * GDL_ERR_ARG, with a message and without a launch or a write: n outside [1, 2^36], a NULL pointer, a misaligned pointer, a
+ * workspace too small.  gdl_pareto_workspace_bytes(n <= 0) = 0. */
+GDL_API size_t gdl_pareto_workspace_bytes(int64_t n);
+GDL_API int gdl_pareto_integrate(float* g_m, const float* g_u, int64_t n, float scale, float* info /* [8], device */, void* ws,
+                                 size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ measurement tap
  * Optional HIP-event timing of every kernel launch (off by default).  While enabled, each
