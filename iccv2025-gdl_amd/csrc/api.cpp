@@ -39,21 +39,23 @@ int gdl_device_info(int* cu_count, char* name, int name_len) {
 static bool dt_ok(int dtype) { return dtype == GDL_F32 || dtype == GDL_BF16; }
 
 int gdl_conv_bn_tiles(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    return conv_tiles_m(dtype, N, H, W, C, K, R, S, stride, pad);
+    return conv_tiles_m(dtype, ConvGeom{N, H, W, C, K, R, S, stride, pad});
 }
 
 size_t gdl_conv_table_bytes(int mode, int N, int H, int W, int R, int S, int stride, int pad) {
-    return gather_table_bytes(mode, N, H, W, R, S, stride, pad);
+    return gather_table_bytes(mode, ConvGeom{N, H, W, 0, 0, R, S, stride, pad});  // (no channel count enters the size)
 }
 int gdl_conv_build_table(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
                          void* table, void* stream) {
     GDL_REQUIRE(dt_ok(dtype) && table && (mode == GATHER_FWD || mode == GATHER_DGRAD), "conv_build_table: bad arguments");
-    return build_gather_table(mode, dtype, N, H, W, C, K, R, S, stride, pad, (GatherEntry*)table, (hipStream_t)stream);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return build_gather_table(mode, dtype, g, (GatherEntry*)table, (hipStream_t)stream);
 }
 int gdl_conv_fwd(int dtype, const void* x, const void* w_krsc, void* y, float* bn_partial, const void* table, int N, int H,
                  int W, int C, int K, int R, int S, int stride, int pad, void* stream) {
     GDL_REQUIRE(x && w_krsc && y, "conv_fwd: null pointer");
-    return conv_fwd(dtype, x, w_krsc, y, bn_partial, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_fwd(dtype, x, w_krsc, y, bn_partial, table, g, (hipStream_t)stream);
 }
 int gdl_bn_act_bits(int dtype, const void* y, const float* scale, const float* shift, const void* res, const float* res_scale,
                     const float* res_shift, void* out, uint8_t* relu_bits, size_t M, int C, void* stream) {
@@ -63,20 +65,23 @@ int gdl_bn_act_bits(int dtype, const void* y, const float* scale, const float* s
 int gdl_conv_dgrad_relu(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const uint8_t* relu_bits,
                         const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, void* stream) {
     GDL_REQUIRE(dy && w_crsk && dx && relu_bits, "conv_dgrad_relu: null pointer");
-    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream, relu_bits);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, g, (hipStream_t)stream, relu_bits);
 }
 int gdl_conv_fwd_bias(int dtype, const void* x, const void* w_krsc, void* y, const float* bias, const void* addend, void* gelu_out,
                       const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, void* stream) {
     GDL_REQUIRE(x && w_krsc && y, "conv_fwd_bias: null pointer");
-    return conv_fwd_bias(dtype, x, w_krsc, y, bias, addend, gelu_out, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_fwd_bias(dtype, x, w_krsc, y, bias, addend, gelu_out, table, g, (hipStream_t)stream);
 }
 int gdl_conv_dgrad_ds(int dtype, const void* dy, const void* w_crsk, const void* dy_ds, const void* w_ds_ck, void* dx,
                       const uint8_t* relu_bits, const void* table, int N, int H, int W, int C, int K, void* stream) {
     GDL_REQUIRE(dy && w_crsk && dy_ds && w_ds_ck && dx, "conv_dgrad_ds: null pointer");
-    return conv_dgrad_ds(dtype, dy, w_crsk, dy_ds, w_ds_ck, dx, table, N, H, W, C, K, (hipStream_t)stream, relu_bits);
+    const ConvGeom g{N, H, W, C, K, 3, 3, 2, 1};  // conv1 of a downsample block
+    return conv_dgrad_ds(dtype, dy, w_crsk, dy_ds, w_ds_ck, dx, table, g, (hipStream_t)stream, relu_bits);
 }
 int gdl_conv_dgrad_bn_tiles(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    return conv_dgrad_tiles_m(dtype, N, H, W, C, K, R, S, stride, pad);
+    return conv_dgrad_tiles_m(dtype, ConvGeom{N, H, W, C, K, R, S, stride, pad});
 }
 int gdl_conv_dgrad_bn(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const uint8_t* relu_bits,
                       const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* y,
@@ -84,16 +89,18 @@ int gdl_conv_dgrad_bn(int dtype, const void* dy, const void* w_crsk, void* dx, c
                       const float* rstd2, float* partial2, void* stream) {
     GDL_REQUIRE(dy && w_crsk && dx && y && mean && rstd && partial, "conv_dgrad_bn: null pointer");
     const BwdStats bw{y, mean, rstd, partial, y2, mean2, rstd2, partial2};
-    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream, relu_bits, &bw);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, g, (hipStream_t)stream, relu_bits, &bw);
 }
 size_t gdl_conv_split_workspace_bytes(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dgrad) {
-    return dt_ok(dtype) ? conv_split_ws_bytes(dtype, N, H, W, C, K, R, S, stride, pad, dgrad) : 0;
+    return dt_ok(dtype) ? conv_split_ws_bytes(dtype, ConvGeom{N, H, W, C, K, R, S, stride, pad}, dgrad) : 0;
 }
 int gdl_conv_fwd_split(int dtype, const void* x, const void* w_krsc, void* y, float* bn_partial, const void* table, int N, int H,
                        int W, int C, int K, int R, int S, int stride, int pad, void* split_ws, size_t split_ws_bytes, void* stream) {
     GDL_REQUIRE(dt_ok(dtype) && x && w_krsc && y && table, "conv_fwd_split: null pointer");
     const SplitWs sk{split_ws, split_ws_bytes};
-    return conv_fwd(dtype, x, w_krsc, y, bn_partial, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream, nullptr, &sk);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_fwd(dtype, x, w_krsc, y, bn_partial, table, g, (hipStream_t)stream, nullptr, &sk);
 }
 int gdl_conv_dgrad_bn_split(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const uint8_t* relu_bits,
                             const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, const void* y,
@@ -102,14 +109,15 @@ int gdl_conv_dgrad_bn_split(int dtype, const void* dy, const void* w_crsk, void*
     GDL_REQUIRE(dt_ok(dtype) && dy && w_crsk && dx && table, "conv_dgrad_bn_split: null pointer");
     const BwdStats bw{y, mean, rstd, partial, y2, mean2, rstd2, partial2};
     const SplitWs sk{split_ws, split_ws_bytes};
-    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream, relu_bits,
-                      y ? &bw : nullptr, &sk);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, g, (hipStream_t)stream, relu_bits, y ? &bw : nullptr, &sk);
 }
 int gdl_conv_dgrad_gelu(int dtype, const void* dy, const void* w_crsk, void* dx, const void* u, void* acc, double scale,
                         const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, void* stream) {
     GDL_REQUIRE(dt_ok(dtype) && dy && w_crsk && dx && u && acc && table && scale > 0.0, "conv_dgrad_gelu: bad arguments");
     const BnAcc a{(long long*)acc, scale, 0.0};
-    return conv_dgrad_gelu(dtype, dy, w_crsk, dx, u, &a, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_dgrad_gelu(dtype, dy, w_crsk, dx, u, &a, table, g, (hipStream_t)stream);
 }
 int gdl_acc_to_float(const void* acc, int n, double inv_scale, float* out, void* stream) {
     GDL_REQUIRE(acc && out && n > 0, "acc_to_float: bad arguments");
@@ -118,17 +126,18 @@ int gdl_acc_to_float(const void* acc, int n, double inv_scale, float* out, void*
 int gdl_conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const void* table, int N,
                    int H, int W, int C, int K, int R, int S, int stride, int pad, void* stream) {
     GDL_REQUIRE(dy && w_crsk && dx, "conv_dgrad: null pointer");
-    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_dgrad(dtype, dy, w_crsk, dx, addend, table, g, (hipStream_t)stream);
 }
 size_t gdl_conv_wgrad_workspace_bytes(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
     (void)dtype;
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    return conv_wgrad_ws_bytes(N * P * Q, C, K, R * S);
+    return conv_wgrad_ws_bytes(ConvGeom{N, H, W, C, K, R, S, stride, pad});
 }
 int gdl_conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* table, int N, int H, int W, int C,
                    int K, int R, int S, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
     GDL_REQUIRE(dy && x && dw, "conv_wgrad: null pointer");
-    return conv_wgrad(dtype, dy, x, dw, table, N, H, W, C, K, R, S, stride, pad, C, ws, ws_bytes, (hipStream_t)stream);
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    return conv_wgrad(dtype, dy, x, dw, table, g, C, ws, ws_bytes, (hipStream_t)stream);
 }
 int gdl_pack_weight(int dtype, const float* w, void* w_krsc, void* w_crsk, int K, int C, int R, int S, void* stream) {
     GDL_REQUIRE(dt_ok(dtype) && w, "pack_weight: bad arguments");

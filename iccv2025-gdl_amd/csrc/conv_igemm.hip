@@ -1875,12 +1875,11 @@ static int pslab_mode() {
 // serve (bias, GELU output / derivative, a forward addend or ReLU bits) move the launch to the round-5 slab kernel; the row queries
 // plan without options, so such an option may only move a launch that writes no partial rows.  (The persistent kernels' other
 // exclusions -- the stride-2 data gradient's row table, the stem's row segments -- never meet their geometry.)
-static int plan_conv(ConvPlan& p, int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
-                     const ConvOpts& o = ConvOpts{}) {
+static int plan_conv(ConvPlan& p, int mode, int dtype, const ConvGeom& g, const ConvOpts& o = ConvOpts{}) {
     const bool fwd = mode == GATHER_FWD, bf = dtype == GDL_BF16;
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    const int M = fwd ? N * P * Q : N * H * W, OC = fwd ? K : C, IC = fwd ? C : K;
-    const bool s1 = R == 3 && S == 3 && stride == 1 && pad == 1;  // the slab kernels' geometry
+    const int N = g.N, H = g.H, W = g.W;
+    const int M = fwd ? g.fwd_rows() : g.dgrad_rows(), OC = fwd ? g.K : g.C, IC = fwd ? g.C : g.K;
+    const bool s1 = g.slab();
     const bool epi = o.bias || o.gelu_out || o.gelu_u || (fwd && (o.addend || o.relu_bits));
     const bool writes_rows = o.stats || (o.bw && o.bw->y);
     p = ConvPlan{ConvKind::FLAT, 0, 0, 2, 0, 0, 1, 0};
@@ -1945,10 +1944,10 @@ static int plan_conv(ConvPlan& p, int mode, int dtype, int N, int H, int W, int 
         // plain GEMMs (1x1, stride 1: the Swin encoder's Linears -- the ResNets have none): the 128x128 tile is the faster one
         // alone (8 DMA pieces per 32 MFMAs instead of 10, each A row gathered for half as many N-tiles), and these run without
         // a second MFMA-bound stream beside them
-        if (R == 1 && S == 1 && stride == 1 && OC % 128 == 0 && (long)((M + 127) / 128) * (OC / 128) >= 256) p.bm = p.bn = 128;
+        if (g.R == 1 && g.S == 1 && g.stride == 1 && OC % 128 == 0 && (long)((M + 127) / 128) * (OC / 128) >= 256) p.bm = p.bn = 128;
     }
     // (the stride-2 data gradient runs over the permuted row table laid out for its M-tile: gather.h)
-    const int mtiles = ceil_div(!fwd && stride == 2 ? dgrad_perm_rows(N, H, W, p.bm) : M, p.bm), ntn = OC / p.bn;
+    const int mtiles = ceil_div(!fwd && g.stride == 2 ? dgrad_perm_rows(N, H, W, p.bm) : M, p.bm), ntn = OC / p.bn;
     p.rows = mtiles;
     // split-K (an alternative path, off in the engine by default): a launch given a workspace runs on this round-5 slab plan,
     // whatever the unsplit launch of this geometry runs on, and keeps the unsplit launch's partial rows
@@ -2112,29 +2111,23 @@ static int launch_mode(ConvArgs& a, const ConvPlan& pl, hipStream_t st) {
 }
 
 // the plan of a launch without options: what the BatchNorm partial-row queries below report (plan_conv cannot fail without options)
-static ConvPlan geometry_plan(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+static ConvPlan geometry_plan(int mode, int dtype, const ConvGeom& g) {
     ConvPlan p;
-    plan_conv(p, mode, dtype, N, H, W, C, K, R, S, stride, pad);
+    plan_conv(p, mode, dtype, g);
     return p;
 }
 // number of M-tiles (= BatchNorm partial rows) the forward kernel of this convolution produces
-int conv_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    return geometry_plan(GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad).rows;
-}
+int conv_tiles_m(int dtype, const ConvGeom& g) { return geometry_plan(GATHER_FWD, dtype, g).rows; }
 // true if the forward of this convolution runs on a persistent kernel (one BatchNorm partial row per block): the in-launch
 // finalize costs a ticket per block LIFE there and is used by default
-bool conv_fwd_persistent(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    const ConvKind k = geometry_plan(GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad).kind;
+bool conv_fwd_persistent(int dtype, const ConvGeom& g) {
+    const ConvKind k = geometry_plan(GATHER_FWD, dtype, g).kind;
     return k == ConvKind::C64 || k == ConvKind::PSLAB;
 }
 // partial rows a data gradient with BatchNorm-backward statistics (ops.h BwdStats) writes
-int conv_dgrad_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    return geometry_plan(GATHER_DGRAD, dtype, N, H, W, C, K, R, S, stride, pad).rows;
-}
+int conv_dgrad_tiles_m(int dtype, const ConvGeom& g) { return geometry_plan(GATHER_DGRAD, dtype, g).rows; }
 // M-tile of a data gradient (the permuted stride-2 table is laid out for it)
-int conv_dgrad_bm(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    return geometry_plan(GATHER_DGRAD, dtype, N, H, W, C, K, R, S, stride, pad).bm;
-}
+int conv_dgrad_bm(int dtype, const ConvGeom& g) { return geometry_plan(GATHER_DGRAD, dtype, g).bm; }
 
 // ---------------------------------------------------------------- split-K finish
 // One block per M-tile of the producing launch (so the per-tile statistics rows keep their count): out[row][c] = what
@@ -2259,27 +2252,26 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(SplitFinArgs f) {
         }
     }
 }
-size_t conv_split_ws_bytes(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dgrad) {
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    const int M = dgrad ? N * H * W : N * P * Q, OC = dgrad ? C : K;
+size_t conv_split_ws_bytes(int dtype, const ConvGeom& g, int dgrad) {
+    const int M = dgrad ? g.dgrad_rows() : g.fwd_rows(), OC = dgrad ? g.C : g.K;
     SplitWs any{&any, 0};  // a workspace of unknown size: how many ways would a launch given one split?
     ConvOpts o;
     o.split = &any;
     ConvPlan pl;
-    plan_conv(pl, dgrad ? GATHER_DGRAD : GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad, o);
+    plan_conv(pl, dgrad ? GATHER_DGRAD : GATHER_FWD, dtype, g, o);
     return pl.split > 1 ? (size_t)pl.split * M * OC * sizeof(float) : 0;
 }
 
-static int run_conv(int mode, int dtype, const void* in, const void* wt, void* out, const void* table, int N, int H, int W, int C,
-                    int K, int R, int S, int stride, int pad, hipStream_t st, const ConvOpts& o = ConvOpts{}) {
+static int run_conv(int mode, int dtype, const void* in, const void* wt, void* out, const void* table, const ConvGeom& cg,
+                    hipStream_t st, const ConvOpts& o = ConvOpts{}) {
     GDL_REQUIRE(dtype == GDL_BF16 || dtype == GDL_F32, "conv: bad dtype %d", dtype);
     GDL_REQUIRE(table, "conv: gather table is null (build it with gdl_conv_build_table)");
     const int bke = (dtype == GDL_BF16) ? 64 : 32;
     const int esz = (dtype == GDL_BF16) ? 2 : 4;
     GatherGeom g;
-    int rc = gather_geom(mode, dtype, N, H, W, C, K, R, S, stride, pad, &g);
+    int rc = gather_geom(mode, dtype, cg, &g);
     if (rc) return rc;
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
+    const int N = cg.N, H = cg.H, W = cg.W, C = cg.C, K = cg.K, R = cg.R, S = cg.S, P = cg.P(), Q = cg.Q();
     const BwdStats* bw = o.bw && o.bw->y ? o.bw : nullptr;
     const bool sacc = o.sacc && o.sacc->acc;
     ConvArgs a{};
@@ -2312,7 +2304,7 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
         a.bw_y2 = bw->y2, a.bw_mean2 = bw->mean2, a.bw_rstd2 = bw->rstd2, a.bw_partial2 = bw->partial2;
     }
     a.table = (const GatherEntry*)table;
-    a.plain = (R == 1 && S == 1 && stride == 1 && pad == 0) ? 1 : 0;
+    a.plain = cg.plain() ? 1 : 0;
     a.M = g.rows;
     a.ntaps = g.ntaps;
     for (int t = 0; t < 9; ++t) a.delta[t] = g.delta[t];
@@ -2334,7 +2326,7 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
         linear_stream_ok(dtype, a.M, a.IC, a.OC, o.addend != nullptr))
         return linear_stream_fwd(in, wt, out, o.addend, o.bias, o.gelu_out, a.M, a.IC, a.OC, st);
     ConvPlan pl;
-    rc = plan_conv(pl, mode, dtype, N, H, W, C, K, R, S, stride, pad, o);
+    rc = plan_conv(pl, mode, dtype, cg, o);
     if (rc) return rc;
     a.flops = 2.0 * (double)N * P * Q * K * C * R * S;  // the convolution's multiply-adds, whatever the direction
     {
@@ -2342,7 +2334,7 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
         a.hbm_bytes = esz * ((double)N * H * W * C + (double)N * P * Q * K + (double)K * C * R * S);
     }
     if (o.dy_ds) {
-        GDL_REQUIRE(mode == GATHER_DGRAD && stride == 2 && R == 3 && S == 3 && pad == 1 && o.w_ds && pl.kind == ConvKind::FLAT,
+        GDL_REQUIRE(mode == GATHER_DGRAD && cg.stride == 2 && R == 3 && S == 3 && cg.pad == 1 && o.w_ds && pl.kind == ConvKind::FLAT,
                     "conv: the folded downsample branch needs the 3x3 stride-2 pad-1 data gradient");
         a.in2 = o.dy_ds;
         a.wt2 = o.w_ds;
@@ -2350,7 +2342,7 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
         a.wt2_bytes = (unsigned)((size_t)K * C * esz);
         a.flops += 2.0 * (double)N * P * Q * K * C;
     }
-    if (mode == GATHER_DGRAD && stride == 2) {
+    if (mode == GATHER_DGRAD && cg.stride == 2) {
         a.orow = (const int*)((const GatherEntry*)table + dgrad_perm_cap(N, H, W));
         a.tile_taps = (const unsigned*)(a.orow + dgrad_perm_cap(N, H, W));
         a.tile_order = (const int*)(a.tile_taps + (dgrad_perm_cap(N, H, W) / 64 + 1));
@@ -2402,11 +2394,11 @@ static int run_conv(int mode, int dtype, const void* in, const void* wt, void* o
     return mode == GATHER_FWD ? launch_mode<float, MODE_FWD>(a, pl, st) : launch_mode<float, MODE_DGRAD>(a, pl, st);
 }
 
-int conv_fwd(int dtype, const void* x, const void* w, void* y, float* bn_partial, const void* table, int N, int H, int W,
-             int C, int K, int R, int S, int stride, int pad, hipStream_t st, const BnAcc* sacc, const SplitWs* split) {
+int conv_fwd(int dtype, const void* x, const void* w, void* y, float* bn_partial, const void* table, const ConvGeom& g,
+             hipStream_t st, const BnAcc* sacc, const SplitWs* split) {
     ConvOpts o;
     o.stats = bn_partial, o.sacc = sacc, o.split = split;
-    return run_conv(GATHER_FWD, dtype, x, w, y, table, N, H, W, C, K, R, S, stride, pad, st, o);
+    return run_conv(GATHER_FWD, dtype, x, w, y, table, g, st, o);
 }
 
 // ---- direct stem forward (layout.hip / gather.h): implicit GEMM over the padded NHWC4 input
@@ -2514,40 +2506,39 @@ int conv_stem_fwd(int dtype, const void* xp, const void* wp, void* y, float* bn_
     return launch_mode<float, MODE_FWD>(a, pl, st);
 }
 
-int conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const void* table, int N, int H,
-               int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st, const uint8_t* relu_bits,
-               const BwdStats* bw, const SplitWs* split) {
+int conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const void* table, const ConvGeom& g,
+               hipStream_t st, const uint8_t* relu_bits, const BwdStats* bw, const SplitWs* split) {
     ConvOpts o;
     o.addend = addend, o.relu_bits = relu_bits, o.bw = bw, o.split = split;
-    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, N, H, W, C, K, R, S, stride, pad, st, o);
+    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, g, st, o);
 }
 
 // dx = dgrad(dy) * gelu'(u), elementwise in the epilogue (u laid out like dx), and the column sums of dx as stored added to
 // the fixed-point accumulators acc (bnacc.h) -- Mlp.fc2's data gradient, the activation's backward and fc1's bias gradient
 // (/root/reference/models/swin_transformer.py:32-47) in one launch
 int conv_dgrad_gelu(int dtype, const void* dy, const void* w_crsk, void* dx, const void* u, const BnAcc* acc, const void* table,
-                    int N, int H, int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st) {
+                    const ConvGeom& g, hipStream_t st) {
     GDL_REQUIRE(u, "conv_dgrad_gelu: null pointer");
     ConvOpts o;
     o.gelu_u = u, o.sacc = acc;
-    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, N, H, W, C, K, R, S, stride, pad, st, o);
+    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, g, st, o);
 }
 
 // forward with the epilogue's bias / residual: y = conv(x, w) + bias (+ addend), each optional (the Swin Linears)
 int conv_fwd_bias(int dtype, const void* x, const void* w, void* y, const float* bias, const void* addend, void* gelu_out,
-                  const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st) {
+                  const void* table, const ConvGeom& g, hipStream_t st) {
     ConvOpts o;
     o.addend = addend, o.bias = bias, o.gelu_out = gelu_out;
-    return run_conv(GATHER_FWD, dtype, x, w, y, table, N, H, W, C, K, R, S, stride, pad, st, o);
+    return run_conv(GATHER_FWD, dtype, x, w, y, table, g, st, o);
 }
 
+// (g is conv1's geometry: run_conv requires the 3x3 stride-2 pad-1 form of a launch that carries the downsample pair)
 int conv_dgrad_ds(int dtype, const void* dy, const void* w_crsk, const void* dy_ds, const void* w_ds_ck, void* dx,
-                  const void* table, int N, int H, int W, int C, int K, hipStream_t st, const uint8_t* relu_bits,
-                  const BwdStats* bw) {
+                  const void* table, const ConvGeom& g, hipStream_t st, const uint8_t* relu_bits, const BwdStats* bw) {
     GDL_REQUIRE(dy_ds && w_ds_ck, "conv_dgrad_ds: null pointer");
     ConvOpts o;
     o.relu_bits = relu_bits, o.dy_ds = dy_ds, o.w_ds = w_ds_ck, o.bw = bw;
-    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, N, H, W, C, K, 3, 3, 2, 1, st, o);
+    return run_conv(GATHER_DGRAD, dtype, dy, w_crsk, dx, table, g, st, o);
 }
 
 }  // namespace gdl

@@ -359,10 +359,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 
 // conv_wgrad9.hip: all 9 taps per block for the 3x3 stride-1 convolutions (bf16)
 bool conv_wgrad9_enabled();
-bool conv_wgrad9_ok(int dtype, int W, int C, int K, int R, int S, int stride, int pad);
+bool conv_wgrad9_ok(int dtype, const ConvGeom& g);
 size_t conv_wgrad9_ws_bytes(int M, int C, int K);
-int conv_wgrad9(const void* dy, const void* x, float* dw, const void* table, int N, int H, int W, int C, int K, void* ws,
-                size_t ws_bytes, hipStream_t st);
+int conv_wgrad9(const void* dy, const void* x, float* dw, const void* table, const ConvGeom& g, void* ws, size_t ws_bytes,
+                hipStream_t st);
 
 // ---------------------------------------------------------------- host side
 struct WgradPlan {
@@ -407,7 +407,8 @@ static WgradPlan plan_wgrad(int M, int C, int K, int RS, bool gemm = false) {
     return p;
 }
 
-size_t conv_wgrad_ws_bytes(int M, int C, int K, int RS) {
+size_t conv_wgrad_ws_bytes(const ConvGeom& g) {
+    const int M = g.fwd_rows(), C = g.C, K = g.K, RS = g.R * g.S;
     const WgradPlan p = plan_wgrad(M, C, K, RS, RS == 1);  // (the larger of the two split targets: an upper bound)
     size_t b = (size_t)p.nsplit * K * RS * C * sizeof(float);
     if (RS == 9 && conv_wgrad9_enabled()) {  // the 9-tap kernel's slices (geometry-independent upper bound)
@@ -438,16 +439,16 @@ static int launch_wg(WgradArgs& a, hipStream_t st) {
     return GDL_OK;
 }
 
-// Cout: number of leading input channels kept in dw (== C unless the channel axis is padded)
-int conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* table, int N, int H, int W, int C, int K,
-               int R, int S, int stride, int pad, int Cout, void* ws, size_t ws_bytes, hipStream_t st) {
+// c_keep: number of leading input channels kept in dw (== C unless the channel axis is padded)
+int conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* table, const ConvGeom& cg, int c_keep, void* ws,
+               size_t ws_bytes, hipStream_t st) {
+    const int N = cg.N, H = cg.H, W = cg.W, C = cg.C, K = cg.K, R = cg.R, S = cg.S;
     GDL_REQUIRE(dtype == GDL_BF16 || dtype == GDL_F32, "wgrad: bad dtype %d", dtype);
     GDL_REQUIRE(table, "wgrad: gather table is null (build it with gdl_conv_build_table)");
     GDL_REQUIRE(C % 64 == 0 && K % 64 == 0, "wgrad: C=%d K=%d must be multiples of 64", C, K);
-    if (Cout == C && conv_wgrad9_ok(dtype, W, C, K, R, S, stride, pad))
-        return conv_wgrad9(dy, x, dw, table, N, H, W, C, K, ws, ws_bytes, st);
+    if (c_keep == C && conv_wgrad9_ok(dtype, cg)) return conv_wgrad9(dy, x, dw, table, cg, ws, ws_bytes, st);
     GatherGeom g;
-    int rc = gather_geom(GATHER_FWD, dtype, N, H, W, C, K, R, S, stride, pad, &g);
+    int rc = gather_geom(GATHER_FWD, dtype, cg, &g);
     if (rc) return rc;
     const int esz = dtype == GDL_BF16 ? 2 : 4;
     WgradArgs a{};
@@ -466,7 +467,7 @@ int conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* 
     GDL_REQUIRE((size_t)a.M * K * esz < (1UL << 31), "wgrad: dy exceeds 2 GiB");
     a.dy_bytes = (unsigned)((size_t)a.M * K * esz);
     a.x_bytes = (unsigned)((size_t)N * H * W * C * esz);
-    const WgradPlan p = plan_wgrad(a.M, C, K, R * S, R == 1 && S == 1 && stride == 1);
+    const WgradPlan p = plan_wgrad(a.M, C, K, R * S, R == 1 && S == 1 && cg.stride == 1);
     a.nsplit = p.nsplit;
     a.chunk = p.chunk;
     a.tiles_k = K / p.tk;
@@ -505,13 +506,13 @@ int conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* 
                    PROF_HBM, st, (double)total * 4.0 * (p.nsplit + 1));
     if (p.nsplit >= 64)
         hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, a.partial, dw,
-                           p.nsplit, K, R * S, C, Cout);
+                           p.nsplit, K, R * S, C, c_keep);
     else if (p.nsplit > 8)
         hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, a.partial, dw,
-                           p.nsplit, K, R * S, C, Cout);
+                           p.nsplit, K, R * S, C, c_keep);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.partial, dw,
-                           p.nsplit, K, R * S, C, Cout);
+                           p.nsplit, K, R * S, C, c_keep);
     GDL_CHECK_LAUNCH("wgrad_reduce_kernel");
     return GDL_OK;
 }

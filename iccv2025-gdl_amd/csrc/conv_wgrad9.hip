@@ -561,13 +561,14 @@ static size_t w9_lds_bytes(int W) {
 }
 
 // true if this geometry runs on the 9-tap kernel
-bool conv_wgrad9_ok(int dtype, int W, int C, int K, int R, int S, int stride, int pad) {
-    return conv_wgrad9_enabled() && dtype == GDL_BF16 && R == 3 && S == 3 && stride == 1 && pad == 1 && C % 64 == 0 &&
-           K % 64 == 0 && w9_lds_bytes(W) <= 96 * 1024;
+bool conv_wgrad9_ok(int dtype, const ConvGeom& g) {
+    return conv_wgrad9_enabled() && dtype == GDL_BF16 && g.slab() && g.C % 64 == 0 && g.K % 64 == 0 &&
+           w9_lds_bytes(g.W) <= 96 * 1024;
 }
 
-int conv_wgrad9(const void* dy, const void* x, float* dw, const void* table, int N, int H, int W, int C, int K, void* ws,
-                size_t ws_bytes, hipStream_t st) {
+int conv_wgrad9(const void* dy, const void* x, float* dw, const void* table, const ConvGeom& g, void* ws, size_t ws_bytes,
+                hipStream_t st) {
+    const int W = g.W, C = g.C, K = g.K;
     Wgrad9Args a{};
 #ifdef GDL_TIMING
     a.dbg = g_timing_buf;
@@ -577,7 +578,7 @@ int conv_wgrad9(const void* dy, const void* x, float* dw, const void* table, int
     a.table = (const GatherEntry*)table;
     a.C = C;
     a.K = K;
-    a.M = N * H * W;
+    a.M = g.fwd_rows();  // (= N * H * W: the slab geometry keeps the spatial size)
     a.W = W;
     GDL_REQUIRE(a.M < (1 << 24), "wgrad: M exceeds 2^24");
     GDL_REQUIRE((size_t)a.M * K * 2 < (1UL << 31) && (size_t)a.M * C * 2 < (1UL << 31), "wgrad: tensor exceeds 2 GiB");

@@ -10,6 +10,7 @@
 //                           y2 = conv2(a1); [yd = convd(x)]; z = relu(bn2(y2) + (bnd(yd) | x)).
 // Backward:  do2 = dz*(z>0); bn2/bnd backward (two passes each); wgrad; dgrad with the identity /
 //            downsample gradient accumulated in the dgrad epilogue.
+#include <algorithm>
 #include <map>
 #include <tuple>
 #include <vector>
@@ -21,9 +22,8 @@ using namespace gdl;
 namespace {
 
 struct Conv {
-    int cin, cout, r, s, stride, pad;
-    int h, w, p, q;  // input / output spatial size
-    int pidx;        // index of the weight in the 60-parameter table
+    ConvGeom g;  // the one geometry its buffers are planned for, its tables built for and its launches run with
+    int pidx;    // index of the weight in the 60-parameter table
     void* w_krsc = nullptr;
     void* w_crsk = nullptr;
     void* tab_fwd = nullptr;    // gather tables (shared between convolutions of equal geometry)
@@ -40,13 +40,25 @@ struct Block {
     Conv c1, c2, cd;
     BN b1, b2, bd;
     bool has_ds = false;
-    int n, h, w, p, q, cin, cout;
+    // [n][h][w][cin] -> [n][p][q][cout]: conv1 reads the block's input, conv2 writes its output's shape
+    int cout() const { return c2.g.K; }
+    size_t in_rows() const { return (size_t)c1.g.dgrad_rows(); }
+    size_t out_rows() const { return (size_t)c2.g.fwd_rows(); }
     void *y1 = nullptr, *a1 = nullptr, *y2 = nullptr, *yd = nullptr, *z = nullptr;
     uint8_t* zbits = nullptr;  // sign bits of z (one byte per 16-byte vector): the backward's ReLU mask, applied by the
                                // data gradient that produces the gradient of z (conv_dgrad's relu_bits)
     uint8_t* abits = nullptr;  // the same for a1 = relu(bn1(y1)): conv2's data gradient stores the masked gradient
     const void* xin = nullptr;
 };
+
+// Key of the gather-table cache: convolutions of equal key share a table.  The table depends on the gathered tensor's row size
+// (its channel count); a stride-2 data-gradient table is permuted for the M-tile its convolution runs with, which depends on
+// the other channel count too -- that one is folded into the key.
+auto table_key(int mode, const ConvGeom& g) {
+    const int src_ch = mode == GATHER_FWD ? g.C : g.K;
+    return std::make_tuple(mode, g.N, g.H, g.W, (mode == GATHER_DGRAD && g.stride == 2) ? src_ch * 4096 + g.C : src_ch, g.R, g.S,
+                           g.stride, g.pad);
+}
 
 struct Bump {
     size_t off = 0;
@@ -121,7 +133,8 @@ struct gdl_encoder {
     int64_t numel[GDL_ENC_NPARAMS];
     // gather tables: geometry -> workspace slot; built lazily on the first forward's stream
     struct TabJob {
-        int mode, N, H, W, C, K, R, S, stride, pad;
+        int mode;
+        ConvGeom g;
         void* dst;
     };
     std::vector<TabJob> tab_jobs;
@@ -151,7 +164,7 @@ size_t gdl_encoder::plan(unsigned char* base) {
     pack_dev = b.take(32 * sizeof(PackDescHost));
     // (per BatchNorm [c][2] sums + its overflow flag word, padded to 16 bytes: bnacc.h)
     size_t acc_ch = 64 + 1;
-    for (const Block& k : blocks) acc_ch += (size_t)(k.cout + 1) * (k.has_ds ? 3 : 2);
+    for (const Block& k : blocks) acc_ch += (size_t)(k.cout() + 1) * (k.has_ds ? 3 : 2);
     acc_bytes = acc_ch * 2 * sizeof(long long);
     acc_arena = (long long*)b.take(acc_bytes);
     size_t acc_used = 0;
@@ -165,26 +178,26 @@ size_t gdl_encoder::plan(unsigned char* base) {
         n.coef = (float*)b.take(sizeof(float) * 2 * n.c);
     };
     auto conv_alloc = [&](Conv& c) {
-        const size_t n = (size_t)c.cout * c.cin * c.r * c.s * e;
+        const size_t n = (size_t)c.g.K * c.g.C * c.g.R * c.g.S * e;
         c.w_krsc = b.take(n);
         c.w_crsk = b.take(n);
     };
     bn_alloc(bn0);
     // gather tables, one per distinct (mode, geometry)
     tab_jobs.clear();
-    std::map<std::tuple<int, int, int, int, int, int, int, int, int>, void*> seen;
-    auto table_for = [&](int mode, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) -> void* {
-        const int src_ch = mode == GATHER_FWD ? C : K;  // the table depends on the gathered tensor's row size
-        // (a stride-2 data-gradient table is permuted for the M-tile its convolution runs with, which
-        // depends on the other channel count too: fold it into the key)
-        auto key = std::make_tuple(mode, N, H, W, (mode == GATHER_DGRAD && stride == 2) ? src_ch * 4096 + C : src_ch, R, S,
-                                   stride, pad);
+    std::map<decltype(table_key(0, ConvGeom{})), void*> seen;
+    auto table_for = [&](int mode, const ConvGeom& g) -> void* {
+        const auto key = table_key(mode, g);
         auto it = seen.find(key);
         if (it != seen.end()) return it->second;
-        void* dst = b.take(gather_table_bytes(mode, N, H, W, R, S, stride, pad));
+        void* dst = b.take(gather_table_bytes(mode, g));
         seen[key] = dst;
-        tab_jobs.push_back(TabJob{mode, N, H, W, C, K, R, S, stride, pad, dst});
+        tab_jobs.push_back(TabJob{mode, g, dst});
         return dst;
+    };
+    auto tables = [&](Conv& c) {
+        c.tab_fwd = table_for(GATHER_FWD, c.g);
+        c.tab_dgrad = table_for(GATHER_DGRAD, c.g);
     };
     tab_stem = b.take((size_t)m0 * sizeof(GatherEntry));
     size_t max_act = (size_t)n_img * h1 * w1 * 64;  // elements
@@ -194,7 +207,7 @@ size_t gdl_encoder::plan(unsigned char* base) {
     size_t wg = conv_stem_wgrad_ws_bytes(n_img, H, W);
     const void* prev = x1;
     for (Block& k : blocks) {
-        const size_t out_el = (size_t)k.n * k.p * k.q * k.cout;
+        const size_t out_el = k.out_rows() * k.cout();
         k.xin = prev;
         k.y1 = b.take(out_el * e);
         k.a1 = b.take(out_el * e);
@@ -204,41 +217,25 @@ size_t gdl_encoder::plan(unsigned char* base) {
         k.abits = (uint8_t*)b.take(out_el * e / 16);
         conv_alloc(k.c1);
         conv_alloc(k.c2);
-        for (Conv* c : {&k.c1, &k.c2}) {
-            c->tab_fwd = table_for(GATHER_FWD, k.n, c->h, c->w, c->cin, c->cout, c->r, c->s, c->stride, c->pad);
-            c->tab_dgrad = table_for(GATHER_DGRAD, k.n, c->h, c->w, c->cin, c->cout, c->r, c->s, c->stride, c->pad);
-        }
+        tables(k.c1);
+        tables(k.c2);
         bn_alloc(k.b1);
         bn_alloc(k.b2);
         if (k.has_ds) {
             k.yd = b.take(out_el * e);
             conv_alloc(k.cd);
-            k.cd.tab_fwd = table_for(GATHER_FWD, k.n, k.cd.h, k.cd.w, k.cd.cin, k.cd.cout, 1, 1, k.cd.stride, 0);
-            k.cd.tab_dgrad = table_for(GATHER_DGRAD, k.n, k.cd.h, k.cd.w, k.cd.cin, k.cd.cout, 1, 1, k.cd.stride, 0);
+            tables(k.cd);
             bn_alloc(k.bd);
         }
-        const size_t in_el = (size_t)k.n * k.h * k.w * k.cin;
-        if (out_el > max_act) max_act = out_el;
-        if (in_el > max_act) max_act = in_el;
-        const int M = k.n * k.p * k.q;
-        for (const Conv* c : {&k.c1, &k.c2, &k.cd}) {
+        for (const Conv* c : {&k.c1, &k.c2, &k.cd}) {  // BatchNorm partial rows of the forwards, weight-gradient workspace
             if (c == &k.cd && !k.has_ds) continue;
-            const size_t tc = (size_t)conv_tiles_m(dtype, k.n, c->h, c->w, c->cin, c->cout, c->r, c->s, c->stride, c->pad) *
-                              c->cout;
-            if (tc > max_tiles_c) max_tiles_c = tc;
+            max_tiles_c = std::max(max_tiles_c, (size_t)conv_tiles_m(dtype, c->g) * c->g.K);
+            wg = std::max(wg, conv_wgrad_ws_bytes(c->g));
         }
-        const size_t bb = (size_t)bn_bwd_blocks((size_t)M, k.cout) * k.cout;
-        if (bb > max_bnb) max_bnb = bb;
-        const size_t ta = (size_t)conv_dgrad_tiles_m(dtype, k.n, k.c2.h, k.c2.w, k.c2.cin, k.c2.cout, 3, 3, 1, 1) * k.cout;
-        const size_t tb = (size_t)conv_dgrad_tiles_m(dtype, k.n, k.c1.h, k.c1.w, k.c1.cin, k.c1.cout, 3, 3, k.c1.stride, 1) * k.cin;
-        if (ta > max_bwt) max_bwt = ta;
-        if (tb > max_bwt) max_bwt = tb;
-        size_t w1 = conv_wgrad_ws_bytes(M, k.cin, k.cout, 9);
-        size_t w2 = conv_wgrad_ws_bytes(M, k.cout, k.cout, 9);
-        size_t w3 = k.has_ds ? conv_wgrad_ws_bytes(M, k.cin, k.cout, 1) : 0;
-        if (w1 > wg) wg = w1;
-        if (w2 > wg) wg = w2;
-        if (w3 > wg) wg = w3;
+        max_act = std::max({max_act, out_el, k.in_rows() * k.c1.g.C});
+        max_bnb = std::max(max_bnb, (size_t)bn_bwd_blocks(k.out_rows(), k.cout()) * k.cout());
+        // (the data gradients of conv2 / conv1 leave the BatchNorm-backward sums of their output's channels)
+        for (const Conv* c : {&k.c2, &k.c1}) max_bwt = std::max(max_bwt, (size_t)conv_dgrad_tiles_m(dtype, c->g) * c->g.C);
         prev = k.z;
     }
     gA = b.take(max_act * e);
@@ -277,8 +274,7 @@ size_t gdl_encoder::plan(unsigned char* base) {
         for (const Block& k : blocks)
             for (const Conv* c : {&k.c1, &k.c2})
                 for (int dg = 0; dg < 2; ++dg) {
-                    const size_t nb = conv_split_ws_bytes(dtype, k.n, c->h, c->w, c->cin, c->cout, c->r, c->s, c->stride, c->pad, dg);
-                    need = nb > need ? nb : need;
+                    need = std::max(need, conv_split_ws_bytes(dtype, c->g, dg));
                 }
         sk.bytes = need;
         sk.ptr = need ? b.take(need) : nullptr;
@@ -331,20 +327,14 @@ int gdl_encoder_create(gdl_encoder_t** out, int modality, int dtype, int B, int 
             const int planes = planes_of[li];
             const int stride = (bk == 0 && li > 0) ? 2 : 1;
             k.has_ds = (stride != 1 || inpl != planes);
-            k.n = e->n_img;
-            k.h = h;
-            k.w = w;
-            k.cin = inpl;
-            k.cout = planes;
-            k.p = (h + 2 - 3) / stride + 1;
-            k.q = (w + 2 - 3) / stride + 1;
-            k.c1 = Conv{inpl, planes, 3, 3, stride, 1, h, w, k.p, k.q, pi};
+            k.c1 = Conv{ConvGeom{e->n_img, h, w, inpl, planes, 3, 3, stride, 1}, pi};
+            const int p = k.c1.g.P(), q = k.c1.g.Q();
             e->numel[pi] = (int64_t)planes * inpl * 9;
             k.b1.c = planes;
             k.b1.pidx = pi + 1;
             k.b1.bidx = bi++;
             e->numel[pi + 1] = e->numel[pi + 2] = planes;
-            k.c2 = Conv{planes, planes, 3, 3, 1, 1, k.p, k.q, k.p, k.q, pi + 3};
+            k.c2 = Conv{ConvGeom{e->n_img, p, q, planes, planes, 3, 3, 1, 1}, pi + 3};
             e->numel[pi + 3] = (int64_t)planes * planes * 9;
             k.b2.c = planes;
             k.b2.pidx = pi + 4;
@@ -352,7 +342,7 @@ int gdl_encoder_create(gdl_encoder_t** out, int modality, int dtype, int B, int 
             e->numel[pi + 4] = e->numel[pi + 5] = planes;
             pi += 6;
             if (k.has_ds) {
-                k.cd = Conv{inpl, planes, 1, 1, stride, 0, h, w, k.p, k.q, pi};
+                k.cd = Conv{ConvGeom{e->n_img, h, w, inpl, planes, 1, 1, stride, 0}, pi};
                 e->numel[pi] = (int64_t)planes * inpl;
                 k.bd.c = planes;
                 k.bd.pidx = pi + 1;
@@ -362,8 +352,8 @@ int gdl_encoder_create(gdl_encoder_t** out, int modality, int dtype, int B, int 
             }
             e->blocks.push_back(k);
             inpl = planes;
-            h = k.p;
-            w = k.q;
+            h = p;
+            w = q;
         }
     }
     e->hf = h;
@@ -603,20 +593,18 @@ static BnFinTrain fin_train_args(gdl_encoder* e, BN& n, const float* partial, in
                       e->nbt[n.bidx], n.mean, n.rstd, n.scale, n.shift};
 }
 
-static int conv_bn(gdl_encoder* e, Conv& c, BN& n, const void* x, void* y, int nimg, int training, hipStream_t st,
+static int conv_bn(gdl_encoder* e, Conv& c, BN& n, const void* x, void* y, int training, hipStream_t st,
                    float* partial = nullptr) {
     const bool sep = separate_stats();
     if (!partial) partial = e->bn_partial;
-    const int M = nimg * c.p * c.q;
+    const int M = c.g.fwd_rows();
     if (sep && training) {
-        RC(conv_fwd(e->dtype, x, c.w_krsc, y, nullptr, c.tab_fwd, nimg, c.h, c.w, c.cin, c.cout, c.r, c.s, c.stride, c.pad, st));
-        RC(bn_stats(e->dtype, y, partial, M, c.cout, st));
+        RC(conv_fwd(e->dtype, x, c.w_krsc, y, nullptr, c.tab_fwd, c.g, st));
+        RC(bn_stats(e->dtype, y, partial, M, c.g.K, st));
         return bn_finalize(e, n, training, bn_stats_tiles(M), (double)M, st);
     }
-    const int tiles = conv_tiles_m(e->dtype, nimg, c.h, c.w, c.cin, c.cout, c.r, c.s, c.stride, c.pad);
-    RC(conv_fwd(e->dtype, x, c.w_krsc, y, training ? partial : nullptr, c.tab_fwd, nimg, c.h, c.w, c.cin, c.cout, c.r, c.s,
-                c.stride, c.pad, st, nullptr, &e->sk));
-    return bn_finalize(e, n, training, tiles, (double)M, st);
+    RC(conv_fwd(e->dtype, x, c.w_krsc, y, training ? partial : nullptr, c.tab_fwd, c.g, st, nullptr, &e->sk));
+    return bn_finalize(e, n, training, conv_tiles_m(e->dtype, c.g), (double)M, st);
 }
 
 int gdl_encoder_forward(gdl_encoder_t* e, const float* x, int training, float* feat_out, float* fmap_nchw,
@@ -635,7 +623,7 @@ int gdl_encoder_forward(gdl_encoder_t* e, const float* x, int training, float* f
     if (e->tabs_dirty) {  // gather tables: once per bound workspace
         RC(build_stem_table(dt, e->n_img, e->H, e->W, stem_taps(dt), (GatherEntry*)e->tab_stem, st));
         for (const gdl_encoder::TabJob& j : e->tab_jobs)
-            RC(build_gather_table(j.mode, dt, j.N, j.H, j.W, j.C, j.K, j.R, j.S, j.stride, j.pad, (GatherEntry*)j.dst, st));
+            RC(build_gather_table(j.mode, dt, j.g, (GatherEntry*)j.dst, st));
         e->tabs_dirty = false;
     }
     if (e->pack_dirty) {  // (re)build the descriptor table of the batched packing launch
@@ -647,12 +635,12 @@ int gdl_encoder_forward(gdl_encoder_t* e, const float* x, int training, float* f
             d.w = e->params[c.pidx];
             d.krsc = c.w_krsc;
             d.crsk = c.w_crsk;
-            d.K = c.cout;
-            d.C = c.cin;
-            d.RS = c.r * c.s;
+            d.K = c.g.K;
+            d.C = c.g.C;
+            d.RS = c.g.R * c.g.S;
             d.blk0 = blk;
-            const size_t total = (size_t)c.cout * c.cin * c.r * c.s;
-            blk += (c.cout / 32) * (c.cin / 32);  // one block per 32x32 (k, c) patch
+            const size_t total = (size_t)c.g.K * c.g.C * c.g.R * c.g.S;
+            blk += (c.g.K / 32) * (c.g.C / 32);  // one block per 32x32 (k, c) patch
             bytes += (double)total * (4.0 + 2.0 * e->esz);
             e->pack_host.push_back(d);
         };
@@ -697,59 +685,56 @@ int gdl_encoder_forward(gdl_encoder_t* e, const float* x, int training, float* f
     }
     // layer1..layer4   (backbone.py:175-178; BasicBlock.forward :52-68)
     for (Block& k : e->blocks) {
-        const size_t Mo = (size_t)k.n * k.p * k.q;
+        const size_t Mo = k.out_rows();
+        const int cout = k.cout();
         if (acc) {  // convolutions add their tiles' sums to the accumulators; the applies derive the constants themselves
             auto conv = [&](const Conv& c, const BN& n, const void* x, void* y) {
-                if (c.stride == 1 && c.r == 3 && (GDL_SKIPPED(65536) || (GDL_SKIPPED(2048) && c.cout == 512))) return (int)GDL_OK;
-                if ((c.stride == 2 || c.r == 1) && GDL_SKIPPED(32768)) return (int)GDL_OK;
-                if (c.r == 1 && GDL_SKIPPED(2097152)) return (int)GDL_OK;  // the shortcut's 1x1 convolutions only
+                if (c.g.stride == 1 && c.g.R == 3 && (GDL_SKIPPED(65536) || (GDL_SKIPPED(2048) && c.g.K == 512))) return (int)GDL_OK;
+                if ((c.g.stride == 2 || c.g.R == 1) && GDL_SKIPPED(32768)) return (int)GDL_OK;
+                if (c.g.R == 1 && GDL_SKIPPED(2097152)) return (int)GDL_OK;  // the shortcut's 1x1 convolutions only
                 const BnAcc pa = acc_producer(n, Mo);
-                return conv_fwd(dt, x, c.w_krsc, y, nullptr, c.tab_fwd, k.n, c.h, c.w, c.cin, c.cout, c.r, c.s, c.stride, c.pad, st,
-                                &pa, &e->sk);
+                return conv_fwd(dt, x, c.w_krsc, y, nullptr, c.tab_fwd, c.g, st, &pa, &e->sk);
             };
             RC(conv(k.c1, k.b1, k.xin, k.y1));
             const BnAccFin f1 = acc_consumer(e, k.b1, Mo), f2 = acc_consumer(e, k.b2, Mo);
-            RC(bn_act(dt, k.y1, k.b1.scale, k.b1.shift, nullptr, nullptr, nullptr, 1, k.a1, Mo, k.cout, st,
+            RC(bn_act(dt, k.y1, k.b1.scale, k.b1.shift, nullptr, nullptr, nullptr, 1, k.a1, Mo, cout, st,
                       bw_fuse_on() ? k.abits : nullptr, &f1));
             RC(conv(k.c2, k.b2, k.a1, k.y2));
             if (k.has_ds) {
                 RC(conv(k.cd, k.bd, k.xin, k.yd));
                 const BnAccFin fd = acc_consumer(e, k.bd, Mo);
-                RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.yd, k.bd.scale, k.bd.shift, 1, k.z, Mo, k.cout, st, k.zbits, &f2, &fd));
+                RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.yd, k.bd.scale, k.bd.shift, 1, k.z, Mo, cout, st, k.zbits, &f2, &fd));
             } else {
-                RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.xin, nullptr, nullptr, 1, k.z, Mo, k.cout, st, k.zbits, &f2));
+                RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.xin, nullptr, nullptr, 1, k.z, Mo, cout, st, k.zbits, &f2));
             }
             continue;
         }
-        RC(conv_bn(e, k.c1, k.b1, k.xin, k.y1, k.n, training, st));
-        if (!(GDL_SKIPPED(1) || (GDL_SKIPPED(2) && k.cout == 64)))
-            RC(bn_act(dt, k.y1, k.b1.scale, k.b1.shift, nullptr, nullptr, nullptr, 1, k.a1, Mo, k.cout, st,
+        RC(conv_bn(e, k.c1, k.b1, k.xin, k.y1, training, st));
+        if (!(GDL_SKIPPED(1) || (GDL_SKIPPED(2) && cout == 64)))
+            RC(bn_act(dt, k.y1, k.b1.scale, k.b1.shift, nullptr, nullptr, nullptr, 1, k.a1, Mo, cout, st,
                       (training && bw_fuse_on()) ? k.abits : nullptr));
         if (k.has_ds && training && !separate_stats()) {
             // bn2 and the downsample BatchNorm are independent: both convolutions first, ONE finalize launch for the two
             // (a finalize kernel costs the chain its whole ~6 us; 80 of them were 0.56 ms of the step)
             auto fin = [&](const Conv& c, BN& n, const float* partial) {
-                return BnFinTrain{partial, conv_tiles_m(dt, k.n, c.h, c.w, c.cin, c.cout, c.r, c.s, c.stride, c.pad), n.c,
-                                  (double)Mo, e->params[n.pidx], e->params[n.pidx + 1], e->rmean[n.bidx], e->rvar[n.bidx],
-                                  e->nbt[n.bidx], n.mean, n.rstd, n.scale, n.shift};
+                return BnFinTrain{partial, conv_tiles_m(dt, c.g), n.c, (double)Mo, e->params[n.pidx], e->params[n.pidx + 1],
+                                  e->rmean[n.bidx], e->rvar[n.bidx], e->nbt[n.bidx], n.mean, n.rstd, n.scale, n.shift};
             };
-            RC(conv_fwd(dt, k.a1, k.c2.w_krsc, k.y2, e->bn_partial, k.c2.tab_fwd, k.n, k.c2.h, k.c2.w, k.c2.cin, k.c2.cout,
-                        k.c2.r, k.c2.s, k.c2.stride, k.c2.pad, st));
-            RC(conv_fwd(dt, k.xin, k.cd.w_krsc, k.yd, e->bn_partial2, k.cd.tab_fwd, k.n, k.cd.h, k.cd.w, k.cd.cin, k.cd.cout,
-                        k.cd.r, k.cd.s, k.cd.stride, k.cd.pad, st));
+            RC(conv_fwd(dt, k.a1, k.c2.w_krsc, k.y2, e->bn_partial, k.c2.tab_fwd, k.c2.g, st));
+            RC(conv_fwd(dt, k.xin, k.cd.w_krsc, k.yd, e->bn_partial2, k.cd.tab_fwd, k.cd.g, st));
             if (!GDL_SKIPPED(16))
                 RC(bn_finalize_train_pair(fin(k.c2, k.b2, e->bn_partial), fin(k.cd, k.bd, e->bn_partial2), 1e-5f, 0.1f, st));
-            RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.yd, k.bd.scale, k.bd.shift, 1, k.z, Mo, k.cout, st,
+            RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.yd, k.bd.scale, k.bd.shift, 1, k.z, Mo, cout, st,
                       training ? k.zbits : nullptr));
             continue;
         }
-        RC(conv_bn(e, k.c2, k.b2, k.a1, k.y2, k.n, training, st));
+        RC(conv_bn(e, k.c2, k.b2, k.a1, k.y2, training, st));
         if (k.has_ds) {
-            RC(conv_bn(e, k.cd, k.bd, k.xin, k.yd, k.n, training, st, e->bn_partial2));
-            RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.yd, k.bd.scale, k.bd.shift, 1, k.z, Mo, k.cout, st,
+            RC(conv_bn(e, k.cd, k.bd, k.xin, k.yd, training, st, e->bn_partial2));
+            RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.yd, k.bd.scale, k.bd.shift, 1, k.z, Mo, cout, st,
                       training ? k.zbits : nullptr));
         } else {
-            RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.xin, nullptr, nullptr, 1, k.z, Mo, k.cout, st,
+            RC(bn_act(dt, k.y2, k.b2.scale, k.b2.shift, k.xin, nullptr, nullptr, 1, k.z, Mo, cout, st,
                       training ? k.zbits : nullptr));
         }
     }
@@ -853,7 +838,8 @@ static int encoder_backward_impl(gdl_encoder* e, const float* dfeat, const float
     };
     for (int bi = bi_first; bi >= bi_last; --bi) {
         Block& k = e->blocks[bi];
-        const size_t Mo = (size_t)k.n * k.p * k.q;
+        const size_t Mo = k.out_rows();
+        const int cout = k.cout();
         const int par = bi & 1;
         void *gB = e->gB[par], *gC = e->gC[par], *gD = e->gD[par];
         if (e->has_side && e->side_pending[par]) {  // the side stream still reads this parity's buffers (two blocks ago)
@@ -865,46 +851,44 @@ static int encoder_backward_impl(gdl_encoder* e, const float* dfeat, const float
         // downsample BatchNorm); then finalize + apply per BatchNorm
         void* do2 = dz;
         {
-            const int blocks = bn_bwd_blocks(Mo, k.cout);
-            const BnFinBwd f2{e->bnb_partial, blocks, k.cout, (double)Mo, grads[k.b2.pidx], grads[k.b2.pidx + 1], k.b2.coef};
-            const BnFinBwd fd{e->bnb_partial2, blocks, k.cout, (double)Mo, k.has_ds ? grads[k.bd.pidx] : nullptr,
+            const int blocks = bn_bwd_blocks(Mo, cout);
+            const BnFinBwd f2{e->bnb_partial, blocks, cout, (double)Mo, grads[k.b2.pidx], grads[k.b2.pidx + 1], k.b2.coef};
+            const BnFinBwd fd{e->bnb_partial2, blocks, cout, (double)Mo, k.has_ds ? grads[k.bd.pidx] : nullptr,
                               k.has_ds ? grads[k.bd.pidx + 1] : nullptr, k.has_ds ? k.bd.coef : nullptr};
             if (b2_rows > 0) {
                 // the sums came with dz (conv1's data gradient of the block behind this one): only the finalize is left
-                const BnFinBwd g2{e->bwB, b2_rows, k.cout, (double)Mo, grads[k.b2.pidx], grads[k.b2.pidx + 1], k.b2.coef};
-                const BnFinBwd gd{e->bwB2, b2_rows, k.cout, (double)Mo, k.has_ds ? grads[k.bd.pidx] : nullptr,
+                const BnFinBwd g2{e->bwB, b2_rows, cout, (double)Mo, grads[k.b2.pidx], grads[k.b2.pidx + 1], k.b2.coef};
+                const BnFinBwd gd{e->bwB2, b2_rows, cout, (double)Mo, k.has_ds ? grads[k.bd.pidx] : nullptr,
                                   k.has_ds ? grads[k.bd.pidx + 1] : nullptr, k.has_ds ? k.bd.coef : nullptr};
                 if ((GDL_SKIPPED(32) || GDL_SKIPPED(262144))) {
                 } else if (k.has_ds)
                     RC(bn_bwd_finalize_pair(g2, gd, st));
                 else
-                    RC(bn_bwd_finalize(g2.partial, g2.blocks, k.cout, (double)Mo, g2.dgamma, g2.dbeta, g2.coef, st));
+                    RC(bn_bwd_finalize(g2.partial, g2.blocks, cout, (double)Mo, g2.dgamma, g2.dbeta, g2.coef, st));
             } else
             RC(block_bwd_reduce(dt, dz, k.z, k.y2, k.has_ds ? k.yd : nullptr, k.b2.mean, k.b2.rstd, k.has_ds ? k.bd.mean : nullptr,
-                                k.has_ds ? k.bd.rstd : nullptr, do2, e->bnb_partial, e->bnb_partial2, Mo, k.cout, st, premasked));
+                                k.has_ds ? k.bd.rstd : nullptr, do2, e->bnb_partial, e->bnb_partial2, Mo, cout, st, premasked));
             if (b2_rows == 0) {
                 if (k.has_ds)  // one finalize launch for bn2 and the downsample BatchNorm
                     RC(bn_bwd_finalize_pair(f2, fd, st));
                 else
-                    RC(bn_bwd_finalize(e->bnb_partial, blocks, k.cout, (double)Mo, grads[k.b2.pidx], grads[k.b2.pidx + 1],
+                    RC(bn_bwd_finalize(e->bnb_partial, blocks, cout, (double)Mo, grads[k.b2.pidx], grads[k.b2.pidx + 1],
                                        k.b2.coef, st));
             }
             if (GDL_SKIPPED(8)) {
             } else if (k.has_ds)  // gB = dy2 and gD = dyd from one pass over do2
                 RC(bn_bwd_apply2(dt, do2, k.y2, k.b2.mean, k.b2.rstd, e->params[k.b2.pidx], k.b2.coef, gB, k.yd, k.bd.mean,
-                                 k.bd.rstd, e->params[k.bd.pidx], k.bd.coef, gD, Mo, k.cout, st));
+                                 k.bd.rstd, e->params[k.bd.pidx], k.bd.coef, gD, Mo, cout, st));
             else
                 RC(bn_bwd_apply(dt, do2, k.y2, k.b2.scale, k.b2.shift, k.b2.mean, k.b2.rstd, e->params[k.b2.pidx], k.b2.coef,
-                                0, gB, Mo, k.cout, st));  // gB = dy2
+                                0, gB, Mo, cout, st));  // gB = dy2
         }
         auto wgrad2 = [&]() -> int {  // weight gradients of conv2 (and of the downsample convolution): need dy2 (dyd)
             RC(fork());
             if (!GDL_SKIPPED(16384))
-            RC(conv_wgrad(dt, gB, k.a1, grads[k.c2.pidx], k.c2.tab_fwd, k.n, k.p, k.q, k.cout, k.cout, 3, 3, 1, 1, k.cout,
-                          e->wg_ws, e->wg_ws_bytes, sw));
+            RC(conv_wgrad(dt, gB, k.a1, grads[k.c2.pidx], k.c2.tab_fwd, k.c2.g, k.c2.g.C, e->wg_ws, e->wg_ws_bytes, sw));
             if (k.has_ds && !GDL_SKIPPED(8192))
-                RC(conv_wgrad(dt, gD, k.xin, grads[k.cd.pidx], k.cd.tab_fwd, k.n, k.h, k.w, k.cin, k.cout, 1, 1, k.cd.stride, 0,
-                              k.cin, e->wg_ws, e->wg_ws_bytes, sw));
+                RC(conv_wgrad(dt, gD, k.xin, grads[k.cd.pidx], k.cd.tab_fwd, k.cd.g, k.cd.g.C, e->wg_ws, e->wg_ws_bytes, sw));
             return GDL_OK;
         };
         // (forking the weight gradients AFTER the data gradient that consumes the same dy -- GDL_WGRAD_LATE -- let them run at their
@@ -913,26 +897,23 @@ static int encoder_backward_impl(gdl_encoder* e, const float* dfeat, const float
         if (fuse) {
             // gC = da1 * (a1 > 0) (sign bits of a1) with bn1's two sums from the epilogue; then finalize + apply
             const BwdStats bwa{k.y1, k.b1.mean, k.b1.rstd, e->bwA, nullptr, nullptr, nullptr, nullptr};
-            if (!(GDL_SKIPPED(131072) || (GDL_SKIPPED(4096) && k.cout == 512)))
-            RC(conv_dgrad(dt, gB, k.c2.w_crsk, gC, nullptr, k.c2.tab_dgrad, k.n, k.p, k.q, k.cout, k.cout, 3, 3, 1, 1, st,
-                          k.abits, &bwa, &e->sk));
-            const int rows = conv_dgrad_tiles_m(dt, k.n, k.p, k.q, k.cout, k.cout, 3, 3, 1, 1);
+            if (!(GDL_SKIPPED(131072) || (GDL_SKIPPED(4096) && cout == 512)))
+            RC(conv_dgrad(dt, gB, k.c2.w_crsk, gC, nullptr, k.c2.tab_dgrad, k.c2.g, st, k.abits, &bwa, &e->sk));
+            const int rows = conv_dgrad_tiles_m(dt, k.c2.g);
             if (!(GDL_SKIPPED(32) || GDL_SKIPPED(262144)))
-                RC(bn_bwd_finalize(e->bwA, rows, k.cout, (double)Mo, grads[k.b1.pidx], grads[k.b1.pidx + 1], k.b1.coef, st));
+                RC(bn_bwd_finalize(e->bwA, rows, cout, (double)Mo, grads[k.b1.pidx], grads[k.b1.pidx + 1], k.b1.coef, st));
             if (!GDL_SKIPPED(4))
             RC(bn_bwd_apply(dt, gC, k.y1, k.b1.scale, k.b1.shift, k.b1.mean, k.b1.rstd, e->params[k.b1.pidx], k.b1.coef, 0, gC, Mo,
-                            k.cout, st));  // gC = dy1 (in place; the gradient is masked already)
+                            cout, st));  // gC = dy1 (in place; the gradient is masked already)
         } else {
-        RC(conv_dgrad(dt, gB, k.c2.w_crsk, gC, nullptr, k.c2.tab_dgrad, k.n, k.p, k.q, k.cout, k.cout, 3, 3, 1, 1,
-                      st, nullptr, nullptr, &e->sk));  // gC = da1
+        RC(conv_dgrad(dt, gB, k.c2.w_crsk, gC, nullptr, k.c2.tab_dgrad, k.c2.g, st, nullptr, nullptr, &e->sk));  // gC = da1
         // relu + bn1 / conv1
         RC(bn_backward(e, k.b1, gC, k.y1, 1, gC, Mo, grads, st));  // gC = dy1 (in place)
         }
         auto wgrad1 = [&]() -> int {  // weight gradient of conv1: needs dy1
             RC(fork());
-            if (!(k.c1.stride == 1 ? GDL_SKIPPED(16384) : GDL_SKIPPED(8192)))
-            RC(conv_wgrad(dt, gC, k.xin, grads[k.c1.pidx], k.c1.tab_fwd, k.n, k.h, k.w, k.cin, k.cout, 3, 3, k.c1.stride, 1,
-                          k.cin, e->wg_ws, e->wg_ws_bytes, sw));
+            if (!(k.c1.g.stride == 1 ? GDL_SKIPPED(16384) : GDL_SKIPPED(8192)))
+            RC(conv_wgrad(dt, gC, k.xin, grads[k.c1.pidx], k.c1.tab_fwd, k.c1.g, k.c1.g.C, e->wg_ws, e->wg_ws_bytes, sw));
             if (e->has_side) {
                 hipError_t he = hipEventRecord(e->ev_side[par], e->side);
                 if (he != hipSuccess) return check_hip(he, "encoder_backward: side event");
@@ -953,29 +934,25 @@ static int encoder_backward_impl(gdl_encoder* e, const float* dfeat, const float
             Block& pv = e->blocks[bi - 1];
             bwb = BwdStats{pv.y2, pv.b2.mean, pv.b2.rstd, e->bwB, pv.has_ds ? pv.yd : nullptr,
                            pv.has_ds ? pv.bd.mean : nullptr, pv.has_ds ? pv.bd.rstd : nullptr, pv.has_ds ? e->bwB2 : nullptr};
-            next_rows = conv_dgrad_tiles_m(dt, k.n, k.h, k.w, k.cin, k.cout, 3, 3, k.c1.stride, 1);
+            next_rows = conv_dgrad_tiles_m(dt, k.c1.g);
         }
         const BwdStats* bwp = next_rows ? &bwb : nullptr;
-        if (k.has_ds && ds_fold_on() && k.c1.stride == 2) {
+        if (k.has_ds && ds_fold_on() && k.c1.g.stride == 2) {
             // the shortcut's 1x1 stride-2 data gradient rides in the 3x3 one as a tenth tap of the (even, even) pixels:
             // one launch and one tensor write instead of two launches, two writes and a read
             if (!GDL_SKIPPED(1024))
-            RC(conv_dgrad_ds(dt, gC, k.c1.w_crsk, gD, k.cd.w_crsk, spare, k.c1.tab_dgrad, k.n, k.h, k.w, k.cin, k.cout, st,
-                             inbits, bwp));
+            RC(conv_dgrad_ds(dt, gC, k.c1.w_crsk, gD, k.cd.w_crsk, spare, k.c1.tab_dgrad, k.c1.g, st, inbits, bwp));
             dxin = spare;
             spare = dz;
         } else if (k.has_ds) {
-            RC(conv_dgrad(dt, gD, k.cd.w_crsk, spare, nullptr, k.cd.tab_dgrad, k.n, k.h, k.w, k.cin, k.cout, 1, 1,
-                          k.cd.stride, 0, st));
-            RC(conv_dgrad(dt, gC, k.c1.w_crsk, spare, spare, k.c1.tab_dgrad, k.n, k.h, k.w, k.cin, k.cout, 3, 3,
-                          k.c1.stride, 1, st, inbits, bwp));
+            RC(conv_dgrad(dt, gD, k.cd.w_crsk, spare, nullptr, k.cd.tab_dgrad, k.cd.g, st));
+            RC(conv_dgrad(dt, gC, k.c1.w_crsk, spare, spare, k.c1.tab_dgrad, k.c1.g, st, inbits, bwp));
             dxin = spare;
             spare = dz;  // the old dz buffer is free now
         } else {
             // identity shortcut: dx = dgrad(conv1) + do2, accumulated in place over do2
-            if (!(GDL_SKIPPED(131072) || (GDL_SKIPPED(4096) && k.cout == 512)))
-            RC(conv_dgrad(dt, gC, k.c1.w_crsk, do2, do2, k.c1.tab_dgrad, k.n, k.h, k.w, k.cin, k.cout, 3, 3, 1, 1, st,
-                          inbits, bwp, &e->sk));
+            if (!(GDL_SKIPPED(131072) || (GDL_SKIPPED(4096) && cout == 512)))
+            RC(conv_dgrad(dt, gC, k.c1.w_crsk, do2, do2, k.c1.tab_dgrad, k.c1.g, st, inbits, bwp, &e->sk));
             dxin = do2;
         }
         premasked = inbits != nullptr;

@@ -31,6 +31,19 @@ struct GatherGeom {
 
 enum { GATHER_FWD = 0, GATHER_DGRAD = 1 };
 
+// A convolution's geometry, in the order of the C ABI's argument list: x [N][H][W][C] -> y [N][P][Q][K] through a K x R x S x C
+// filter.  Host side only -- the kernels take ConvArgs.  One object from the query that sizes a buffer to the launch that
+// writes it, so the two cannot disagree.
+struct ConvGeom {
+    int N, H, W, C, K, R, S, stride, pad;
+    int P() const { return (H + 2 * pad - R) / stride + 1; }
+    int Q() const { return (W + 2 * pad - S) / stride + 1; }
+    int fwd_rows() const { return N * P() * Q(); }  // GEMM rows of the forward (and of the weight gradient): output pixels
+    int dgrad_rows() const { return N * H * W; }    // GEMM rows of the data gradient: input pixels
+    bool slab() const { return R == 3 && S == 3 && stride == 1 && pad == 1; }   // the slab kernels' geometry
+    bool plain() const { return R == 1 && S == 1 && stride == 1 && pad == 0; }  // a plain GEMM
+};
+
 // Stride-2 data gradients use a PERMUTED table: the input pixels (GEMM rows) are grouped by the parity
 // class (h&1, w&1) -- only taps of matching parity reach a pixel, 1 / 2 / 2 / 4 of the 9 taps of a 3x3
 // kernel and none at all for three of the four classes of a 1x1 -- each class padded to a multiple of
@@ -42,16 +55,16 @@ enum { GATHER_FWD = 0, GATHER_DGRAD = 1 };
 inline size_t dgrad_perm_cap(int N, int H, int W) { return (size_t)N * H * W + 4 * 256; }
 // number of GEMM rows of the permuted table for M-tile bm
 int dgrad_perm_rows(int N, int H, int W, int bm);
-int build_dgrad_perm_table(int dtype, int N, int H, int W, int C, int K, int R, int S, int pad, int bm, GatherEntry* table,
-                           hipStream_t st);
+int build_dgrad_perm_table(int dtype, const ConvGeom& g, int bm, GatherEntry* table, hipStream_t st);
 // direct stem (layout.hip): rows = output pixels (n,p,q), off0 = byte offset of padded pixel (n, 2p, 2q)
 int build_stem_table(int dtype, int n_img, int H, int W, int ntaps, GatherEntry* table, hipStream_t st);
 // bytes of a table (any mode / stride)
-size_t gather_table_bytes(int mode, int N, int H, int W, int R, int S, int stride, int pad);
+size_t gather_table_bytes(int mode, const ConvGeom& g);
 
 // fills `g`; returns GDL_OK or an error
-int gather_geom(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, GatherGeom* g);
-int build_gather_table(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
-                       GatherEntry* table, hipStream_t st);
+int gather_geom(int mode, int dtype, const ConvGeom& cg, GatherGeom* g);
+int build_gather_table(int mode, int dtype, const ConvGeom& g, GatherEntry* table, hipStream_t st);
+// M-tile of a data gradient (conv_igemm.hip): the permuted stride-2 table is laid out for it
+int conv_dgrad_bm(int dtype, const ConvGeom& g);
 
 }  // namespace gdl

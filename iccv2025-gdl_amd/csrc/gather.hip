@@ -4,11 +4,12 @@
 
 namespace gdl {
 
-int gather_geom(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, GatherGeom* g) {
+int gather_geom(int mode, int dtype, const ConvGeom& cg, GatherGeom* g) {
+    const int N = cg.N, H = cg.H, W = cg.W, C = cg.C, K = cg.K, R = cg.R, S = cg.S, stride = cg.stride;
     GDL_REQUIRE(R * S <= 9 && R >= 1 && S >= 1, "gather: %dx%d taps unsupported", R, S);
     GDL_REQUIRE(stride == 1 || stride == 2, "gather: stride %d unsupported", stride);
     const int esz = dtype == GDL_BF16 ? 2 : 4;
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
+    const int P = cg.P(), Q = cg.Q();
     g->ntaps = R * S;
     for (int t = 0; t < 9; ++t) g->delta[t] = 0;
     if (mode == GATHER_FWD) {
@@ -58,24 +59,18 @@ __global__ void gather_table_kernel(GatherEntry* __restrict__ tab, int mode, int
     tab[m] = e;
 }
 
-int conv_dgrad_bm(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad);  // conv_igemm.hip
-
-int build_gather_table(int mode, int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
-                       GatherEntry* table, hipStream_t st) {
-    if (mode == GATHER_DGRAD && stride == 2)
-        return build_dgrad_perm_table(dtype, N, H, W, C, K, R, S, pad, conv_dgrad_bm(dtype, N, H, W, C, K, R, S, stride, pad),
-                                      table, st);
+int build_gather_table(int mode, int dtype, const ConvGeom& cg, GatherEntry* table, hipStream_t st) {
+    if (mode == GATHER_DGRAD && cg.stride == 2) return build_dgrad_perm_table(dtype, cg, conv_dgrad_bm(dtype, cg), table, st);
     GatherGeom g;
-    int rc = gather_geom(mode, dtype, N, H, W, C, K, R, S, stride, pad, &g);
+    int rc = gather_geom(mode, dtype, cg, &g);
     if (rc) return rc;
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
     const int grid = ceil_div(g.rows, 256);
     if (mode == GATHER_FWD)
-        hipLaunchKernelGGL(gather_table_kernel, dim3(grid), dim3(256), 0, st, table, mode, g.rows, H, W, P, Q, R, S, stride,
-                           pad, g.row_bytes);
+        hipLaunchKernelGGL(gather_table_kernel, dim3(grid), dim3(256), 0, st, table, mode, g.rows, cg.H, cg.W, cg.P(), cg.Q(), cg.R,
+                           cg.S, cg.stride, cg.pad, g.row_bytes);
     else
-        hipLaunchKernelGGL(gather_table_kernel, dim3(grid), dim3(256), 0, st, table, mode, g.rows, P, Q, H, W, R, S, stride,
-                           pad, g.row_bytes);
+        hipLaunchKernelGGL(gather_table_kernel, dim3(grid), dim3(256), 0, st, table, mode, g.rows, cg.P(), cg.Q(), cg.H, cg.W, cg.R,
+                           cg.S, cg.stride, cg.pad, g.row_bytes);
     GDL_CHECK_LAUNCH("gather_table_kernel");
     return GDL_OK;
 }
@@ -123,10 +118,10 @@ static PermGeom perm_geom(int N, int H, int W, int bm) {
 }
 int dgrad_perm_rows(int N, int H, int W, int bm) { return perm_geom(N, H, W, bm).seg[4]; }
 
-size_t gather_table_bytes(int mode, int N, int H, int W, int R, int S, int stride, int pad) {
-    const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-    if (mode == GATHER_FWD) return (size_t)N * P * Q * sizeof(GatherEntry);
-    if (stride == 2) return dgrad_perm_cap(N, H, W) * (sizeof(GatherEntry) + sizeof(int)) + (dgrad_perm_cap(N, H, W) / 64 + 1) * 8;
+size_t gather_table_bytes(int mode, const ConvGeom& g) {
+    const int N = g.N, H = g.H, W = g.W;
+    if (mode == GATHER_FWD) return (size_t)N * g.P() * g.Q() * sizeof(GatherEntry);
+    if (g.stride == 2) return dgrad_perm_cap(N, H, W) * (sizeof(GatherEntry) + sizeof(int)) + (dgrad_perm_cap(N, H, W) / 64 + 1) * 8;
     return (size_t)N * H * W * sizeof(GatherEntry);
 }
 
@@ -190,12 +185,11 @@ __global__ void dgrad_perm_order_kernel(int* __restrict__ order, PermGeom pg, in
     }
 }
 
-int build_dgrad_perm_table(int dtype, int N, int H, int W, int C, int K, int R, int S, int pad, int bm, GatherEntry* table,
-                           hipStream_t st) {
+int build_dgrad_perm_table(int dtype, const ConvGeom& cg, int bm, GatherEntry* table, hipStream_t st) {
+    const int N = cg.N, H = cg.H, W = cg.W;  // (cg.stride == 2: build_gather_table)
     GatherGeom g;
-    int rc = gather_geom(GATHER_DGRAD, dtype, N, H, W, C, K, R, S, 2, pad, &g);
+    int rc = gather_geom(GATHER_DGRAD, dtype, cg, &g);
     if (rc) return rc;
-    const int P = (H + 2 * pad - R) / 2 + 1, Q = (W + 2 * pad - S) / 2 + 1;
     const PermGeom pg = perm_geom(N, H, W, bm);
     GDL_REQUIRE((size_t)pg.seg[4] <= dgrad_perm_cap(N, H, W), "gather: permuted table overflow");
     const size_t cap = dgrad_perm_cap(N, H, W);
@@ -204,7 +198,7 @@ int build_dgrad_perm_table(int dtype, int N, int H, int W, int C, int K, int R, 
     hipError_t he = hipMemsetAsync(ttaps, 0, (cap / 64 + 1) * 4, st);
     if (he != hipSuccess) return check_hip(he, "hipMemsetAsync(tile taps)");
     hipLaunchKernelGGL(dgrad_perm_table_kernel, dim3(ceil_div(pg.seg[4], 256)), dim3(256), 0, st, table, orow, ttaps, bm, pg, N,
-                       H, W, P, Q, R, S, pad, g.row_bytes);
+                       H, W, cg.P(), cg.Q(), cg.R, cg.S, cg.pad, g.row_bytes);
     GDL_CHECK_LAUNCH("dgrad_perm_table_kernel");
     hipLaunchKernelGGL(dgrad_perm_order_kernel, dim3(1), dim3(1), 0, st, (int*)(ttaps + (cap / 64 + 1)), pg, bm);
     GDL_CHECK_LAUNCH("dgrad_perm_order_kernel");

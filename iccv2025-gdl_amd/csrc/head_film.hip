@@ -228,6 +228,8 @@ struct FilmWs {
     void *tab_a, *tab_p, *wg;
     size_t wg_bytes, total;
 };
+// the head's contractions over fc.weight as plain GEMMs of the convolution kernels: FROWS rows, C -> K channels
+static ConvGeom film_gemm(int C, int K) { return ConvGeom{1, FROWS, 1, C, K, 1, 1, 1, 0}; }
 static FilmWs film_layout(unsigned char* base, int B) {
     const int Bp = film_bp(B);
     FilmWs w{};
@@ -244,9 +246,9 @@ static FilmWs film_layout(unsigned char* base, int B) {
     w.out2 = (float*)take((size_t)2 * Bp * FD * 4);
     w.P = (float*)take((size_t)FROWS * 3 * Bp * 4);
     w.Z = (float*)take((size_t)FD * 3 * Bp * 4);
-    w.tab_a = take(gather_table_bytes(GATHER_FWD, 1, FROWS, 1, 1, 1, 1, 0));
-    w.tab_p = take(gather_table_bytes(GATHER_FWD, 1, FROWS, 1, 1, 1, 1, 0));
-    w.wg_bytes = conv_wgrad_ws_bytes(FROWS, FD, 2 * Bp, 1);
+    w.tab_a = take(gather_table_bytes(GATHER_FWD, film_gemm(FD, 2 * Bp)));  // (a table's size depends on the rows alone)
+    w.tab_p = take(gather_table_bytes(GATHER_FWD, film_gemm(FD, 2 * Bp)));
+    w.wg_bytes = conv_wgrad_ws_bytes(film_gemm(FD, 2 * Bp));
     w.wg = take(w.wg_bytes);
     w.total = off;
     return w;
@@ -266,10 +268,10 @@ int head_film_fwd(const float* x, const float* y, const float* Wfc, const float*
     float *hx = hidden, *hf = hidden + (size_t)B * FD, *hy = hidden + (size_t)2 * B * FD;
     hipLaunchKernelGGL(film_v_kernel, dim3(2 * Bp), dim3(256), 0, st, x, y, w.V, B, Bp, 0);
     GDL_CHECK_LAUNCH("film_v_kernel");
-    int rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, FD, 2 * Bp, 1, 1, 1, 0, (GatherEntry*)w.tab_a, st);
+    int rc = build_gather_table(GATHER_FWD, GDL_F32, film_gemm(FD, 2 * Bp), (GatherEntry*)w.tab_a, st);
     if (rc) return rc;
     // T[(k,i)][col] = sum_j A[(k,i)][j] V[col][j]
-    rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, 1, FROWS, 1, FD, 2 * Bp, 1, 1, 1, 0, st);
+    rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, film_gemm(FD, 2 * Bp), st);
     if (rc) return rc;
     hipLaunchKernelGGL(film_h_kernel, dim3(FD, 3, (B + 63) / 64), dim3(256), 0, st, w.T, x, y, bfc, hx, hf, hy, B, 2 * Bp, Bp, 0);
     GDL_CHECK_LAUNCH("film_h_kernel");
@@ -303,7 +305,7 @@ int head_film_bwd(const float* x, const float* y, const float* Wfc, const float*
         hipLaunchKernelGGL(film_u_kernel<true>, dim3(4096), dim3(256), 0, st, w.dh, x, y, w.U, B, Bp);
         GDL_CHECK_LAUNCH("film_u_kernel");
         // out2[col][i] = sum_(k,j) U[(k,j)][col] A[(k,j)][i]
-        rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, 1, FROWS, 1, FD, 2 * Bp, 1, 1, 1, 0, FD, w.wg, w.wg_bytes, st);
+        rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, film_gemm(FD, 2 * Bp), FD, w.wg, w.wg_bytes, st);
         if (rc) return rc;
         hipLaunchKernelGGL(film_dxy_kernel, dim3(B, 2), dim3(256), 0, st, w.T, w.dh, w.out2, dx, dy, B, Bp);
         GDL_CHECK_LAUNCH("film_dxy_kernel");
@@ -314,10 +316,10 @@ int head_film_bwd(const float* x, const float* y, const float* Wfc, const float*
         GDL_CHECK_LAUNCH("film_p_kernel");
         hipLaunchKernelGGL(film_z_kernel, dim3(FD), dim3(128), 0, st, x, y, w.Z, B, Bp, nblk);
         GDL_CHECK_LAUNCH("film_z_kernel");
-        rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, nblk * Bp, FD, 1, 1, 1, 0, (GatherEntry*)w.tab_p, st);
+        rc = build_gather_table(GATHER_FWD, GDL_F32, film_gemm(nblk * Bp, FD), (GatherEntry*)w.tab_p, st);
         if (rc) return rc;
         // dA[(k,i)][j] = sum_c P[(k,i)][c] Z[j][c]
-        rc = conv_fwd(GDL_F32, w.P, w.Z, dWfc, nullptr, w.tab_p, 1, FROWS, 1, nblk * Bp, FD, 1, 1, 1, 0, st);
+        rc = conv_fwd(GDL_F32, w.P, w.Z, dWfc, nullptr, w.tab_p, film_gemm(nblk * Bp, FD), st);
         if (rc) return rc;
         hipLaunchKernelGGL(film_dbfc_kernel, dim3(2), dim3(256), 0, st, w.dh, uni, dbfc, B);
         GDL_CHECK_LAUNCH("film_dbfc_kernel");
@@ -370,10 +372,10 @@ int head_film_joint_fwd(const float* x, const float* y, const float* Wfc, const 
     const int Bj = film_bj(B);  // <= 2 * Bp: V, T, U and out2 of the DGL layout hold the Bj-column forms
     hipLaunchKernelGGL(film_v_kernel, dim3(Bj), dim3(256), 0, st, (const float*)nullptr, y, w.V, B, Bj, 1);
     GDL_CHECK_LAUNCH("film_v_kernel");
-    int rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, (GatherEntry*)w.tab_a, st);
+    int rc = build_gather_table(GATHER_FWD, GDL_F32, film_gemm(FD, Bj), (GatherEntry*)w.tab_a, st);
     if (rc) return rc;
     // T[(k,i)][b] = sum_j A[(k,i)][j] y_b[j]
-    rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, st);
+    rc = conv_fwd(GDL_F32, Wfc, w.V, w.T, nullptr, w.tab_a, film_gemm(FD, Bj), st);
     if (rc) return rc;
     hipLaunchKernelGGL(film_h_kernel, dim3(FD, 1, (B + 63) / 64), dim3(256), 0, st, w.T, x, y, bfc, (float*)nullptr, hidden,
                        (float*)nullptr, B, Bj, 0, 1);
@@ -409,7 +411,7 @@ int head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const 
         hipLaunchKernelGGL(film_u_kernel<false>, dim3(4096), dim3(256), 0, st, dhf, x, (const float*)nullptr, w.U, B, Bj);
         GDL_CHECK_LAUNCH("film_u_kernel");
         // out2[b][j] = sum_(k,i) U[(k,i)][b] A[(k,i)][j]; the split partials go to the (not yet written) P piece
-        rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, 1, FROWS, 1, FD, Bj, 1, 1, 1, 0, FD, w.P, (size_t)FROWS * 3 * Bp * 4, st);
+        rc = conv_wgrad(GDL_F32, w.U, Wfc, w.out2, w.tab_a, film_gemm(FD, Bj), FD, w.P, (size_t)FROWS * 3 * Bp * 4, st);
         if (rc) return rc;
         hipLaunchKernelGGL(film_joint_dxy_kernel, dim3(FD, (B + 63) / 64), dim3(256), 0, st, w.T, dhf, w.out2, dx, dy, B, Bj);
         GDL_CHECK_LAUNCH("film_joint_dxy_kernel");
@@ -419,9 +421,9 @@ int head_film_joint_bwd(const float* x, const float* y, const float* Wfc, const 
         GDL_CHECK_LAUNCH("film_p_kernel");
         hipLaunchKernelGGL(film_z_kernel, dim3(FD), dim3(128), 0, st, x, y, w.Z, B, Bp, 1);
         GDL_CHECK_LAUNCH("film_z_kernel");
-        rc = build_gather_table(GATHER_FWD, GDL_F32, 1, FROWS, 1, Bp, FD, 1, 1, 1, 0, (GatherEntry*)w.tab_p, st);
+        rc = build_gather_table(GATHER_FWD, GDL_F32, film_gemm(Bp, FD), (GatherEntry*)w.tab_p, st);
         if (rc) return rc;
-        rc = conv_fwd(GDL_F32, w.P, w.Z, dWfc, nullptr, w.tab_p, 1, FROWS, 1, Bp, FD, 1, 1, 1, 0, st);
+        rc = conv_fwd(GDL_F32, w.P, w.Z, dWfc, nullptr, w.tab_p, film_gemm(Bp, FD), st);
         if (rc) return rc;
         hipLaunchKernelGGL(film_dbfc_kernel, dim3(2), dim3(256), 0, st, w.dh, 0, dbfc, B);
         GDL_CHECK_LAUNCH("film_dbfc_kernel");

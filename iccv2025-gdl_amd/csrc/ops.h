@@ -51,7 +51,7 @@ struct SplitWs {
     void* ptr;
     size_t bytes;
 };
-size_t conv_split_ws_bytes(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dgrad);
+size_t conv_split_ws_bytes(int dtype, const ConvGeom& g, int dgrad);
 // linear_stream.hip: out[M][N] = A[M][K] W[N][K]^T (+ bias) (+ addend), optional gelu_out -- bf16, K = 128 / 192 (Swin Linears)
 bool linear_stream_ok(int dtype, int M, int K, int N, bool has_addend);
 int linear_stream_fwd(const void* A, const void* W, void* out, const void* addend, const float* bias, void* gelu_out, int M, int K,
@@ -59,26 +59,25 @@ int linear_stream_fwd(const void* A, const void* W, void* out, const void* adden
 // conv_igemm.hip.  The BatchNorm partial rows a forward / data gradient writes (per M-tile, or per block of a persistent kernel):
 // plan_conv's ConvPlan::rows for the geometry alone -- options that move a launch to another kernel only move launches that
 // write no partial rows, and a split-K launch keeps the unsplit count (the rows past its M-tiles are zeroed)
-int conv_dgrad_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
-int conv_tiles_m(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
-int conv_fwd(int dtype, const void* x, const void* w_krsc, void* y, float* bn_partial, const void* table, int N, int H,
-             int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st, const BnAcc* sacc = nullptr,
-             const SplitWs* split = nullptr);
+int conv_dgrad_tiles_m(int dtype, const ConvGeom& g);
+int conv_tiles_m(int dtype, const ConvGeom& g);
+int conv_fwd(int dtype, const void* x, const void* w_krsc, void* y, float* bn_partial, const void* table, const ConvGeom& g,
+             hipStream_t st, const BnAcc* sacc = nullptr, const SplitWs* split = nullptr);
 int conv_fwd_bias(int dtype, const void* x, const void* w_krsc, void* y, const float* bias, const void* addend, void* gelu_out,
-                  const void* table, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st);
+                  const void* table, const ConvGeom& g, hipStream_t st);
 // relu_bits (optional): sign bits of the tensor whose gradient dx is (bn_act's relu_bits): dx = bit ? dx (+ addend) : 0
-int conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const void* table, int N, int H,
-               int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st, const uint8_t* relu_bits = nullptr,
-               const BwdStats* bw = nullptr, const SplitWs* split = nullptr);
+int conv_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, const void* table, const ConvGeom& g,
+               hipStream_t st, const uint8_t* relu_bits = nullptr, const BwdStats* bw = nullptr, const SplitWs* split = nullptr);
 // dx = dgrad(dy) * gelu'(u) with the column sums of dx (as stored) added to the fixed-point accumulators `acc` (bnacc.h)
 int conv_dgrad_gelu(int dtype, const void* dy, const void* w_crsk, void* dx, const void* u, const BnAcc* acc, const void* table,
-                    int N, int H, int W, int C, int K, int R, int S, int stride, int pad, hipStream_t st);
+                    const ConvGeom& g, hipStream_t st);
 // out[c] = acc[2c] * inv_scale
 int acc_to_float(const long long* acc, int n, double inv_scale, float* out, hipStream_t st);
 // the 3x3 stride-2 pad-1 data gradient of a downsample block's conv1 with the 1x1 stride-2 data gradient of its shortcut
-// convolution folded in: dx = dgrad(dy, w_crsk) + dgrad_1x1s2(dy_ds, w_ds_ck) (+ relu_bits), one launch, no addend pass
+// convolution folded in: dx = dgrad(dy, w_crsk) + dgrad_1x1s2(dy_ds, w_ds_ck) (+ relu_bits), one launch, no addend pass.
+// g: conv1's geometry (required: 3x3, stride 2, pad 1)
 int conv_dgrad_ds(int dtype, const void* dy, const void* w_crsk, const void* dy_ds, const void* w_ds_ck, void* dx,
-                  const void* table, int N, int H, int W, int C, int K, hipStream_t st, const uint8_t* relu_bits = nullptr,
+                  const void* table, const ConvGeom& g, hipStream_t st, const uint8_t* relu_bits = nullptr,
                   const BwdStats* bw = nullptr);
 // direct (implicit-GEMM) stem: layout.hip (padded NHWC4 input, row-wise weights), gather.hip (table),
 // conv_igemm.hip (forward), conv_wgrad.hip (weight gradient)
@@ -90,7 +89,7 @@ int stem_pad(int dtype, const float* x, void* xp, int B, int Cin, int T, int H, 
              size_t zero_bytes = 0);
 int pack_stem_rows(int dtype, const float* w, void* wp, int cin, hipStream_t st);
 int conv_stem_tiles_m(int dtype, int n_img, int H, int W);
-bool conv_fwd_persistent(int dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
+bool conv_fwd_persistent(int dtype, const ConvGeom& g);
 bool conv_stem_persistent(int dtype, int W);
 int conv_stem_fwd(int dtype, const void* xp, const void* wp, void* y, float* bn_partial, const void* table, int n_img, int H,
                   int W, int Cin, hipStream_t st, const BnAcc* sacc = nullptr);
@@ -103,9 +102,10 @@ int stem_bwd_fused(const void* dz, const uint8_t* idx, const void* y0, const flo
                    const float* rstd, const float* gamma, const float* coef, const void* xp, float* dw, int n_img, int H, int W,
                    int Cin, void* ws, size_t ws_bytes, hipStream_t st);
 // conv_wgrad.hip
-size_t conv_wgrad_ws_bytes(int M, int C, int K, int RS);
-int conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* table, int N, int H, int W, int C, int K,
-               int R, int S, int stride, int pad, int Cout, void* ws, size_t ws_bytes, hipStream_t st);
+size_t conv_wgrad_ws_bytes(const ConvGeom& g);
+// c_keep: number of leading input channels kept in dw (== g.C unless the channel axis is padded)
+int conv_wgrad(int dtype, const void* dy, const void* x, float* dw, const void* table, const ConvGeom& g, int c_keep, void* ws,
+               size_t ws_bytes, hipStream_t st);
 // layout.hip
 int pack_weight(int dtype, const float* w, void* krsc, void* crsk, int K, int C, int R, int S, hipStream_t st);
 struct PackDescHost {  // mirrors layout.hip::PackDesc
