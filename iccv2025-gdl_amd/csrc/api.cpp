@@ -243,6 +243,110 @@ int gdl_bn_relu_maxpool_fwd(int dtype, const void* y, const float* scale, const 
     GDL_REQUIRE(dt_ok(dtype) && y && scale && shift && out && idx, "bn_relu_maxpool_fwd: bad arguments");
     return bn_relu_maxpool_fwd(dtype, y, scale, shift, out, idx, ymax, N, H, W, C, (hipStream_t)stream);
 }
+// ---- the fused forms the encoder engine launches, one entry point per kernel so that each can be tested alone
+// (tests/test_bnacc_gpu.py).  Accumulator buffers follow the engine's arena convention: int64 [C][2] + one flag word.
+static BnAcc acc_producer_of(int64_t* acc, int C, size_t rows) {
+    BnAcc a{(long long*)acc, 0.0, 0.0, (long long*)acc + 2 * (size_t)C};
+    bn_acc_scales(rows, &a.s1, &a.s2);
+    return a;
+}
+static BnAccFin acc_consumer_of(const int64_t* acc, int C, size_t rows, const float* gamma, const float* beta, float* rm, float* rv,
+                                int64_t* nbt, float* save_mean, float* save_rstd, float* scale, float* shift, float eps,
+                                float momentum) {
+    double s1, s2;
+    bn_acc_scales(rows, &s1, &s2);
+    return BnAccFin{(const long long*)acc, 1.0 / s1, 1.0 / s2, (double)rows, gamma, beta, rm, rv, nbt, save_mean, save_rstd, scale,
+                    shift, eps, momentum, acc ? (const long long*)acc + 2 * (size_t)C : nullptr};
+}
+int gdl_bn_acc_scales(size_t rows, double* s1, double* s2) {
+    GDL_REQUIRE(s1 && s2 && rows >= 1, "bn_acc_scales: bad arguments");
+    bn_acc_scales(rows, s1, s2);
+    return GDL_OK;
+}
+int gdl_conv_fwd_acc(int dtype, const void* x, const void* w_krsc, void* y, int64_t* acc, const void* table, int N, int H, int W,
+                     int C, int K, int R, int S, int stride, int pad, void* split_ws, size_t split_ws_bytes, void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && x && w_krsc && y && acc && stride >= 1, "conv_fwd_acc: bad arguments");
+    const ConvGeom g{N, H, W, C, K, R, S, stride, pad};
+    const size_t rows = (size_t)N * ((H + 2 * pad - R) / stride + 1) * ((W + 2 * pad - S) / stride + 1);
+    const BnAcc a = acc_producer_of(acc, K, rows);
+    const SplitWs sk{split_ws, split_ws_bytes};
+    return conv_fwd(dtype, x, w_krsc, y, nullptr, table, g, (hipStream_t)stream, &a, split_ws ? &sk : nullptr);
+}
+int gdl_stem_conv_fwd_acc(int dtype, const void* xp, const void* wp, void* y, int64_t* acc, const void* table, int n_img, int H,
+                          int W, int Cin, void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && acc, "stem_conv_fwd_acc: bad arguments");
+    const BnAcc a = acc_producer_of(acc, 64, (size_t)n_img * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1));
+    return conv_stem_fwd(dtype, xp, wp, y, nullptr, table, n_img, H, W, Cin, (hipStream_t)stream, &a);
+}
+int gdl_stem_pad_zero(int dtype, const float* x, void* xp, int B, int Cin, int T, int H, int W, void* zero, size_t zero_bytes,
+                      void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && x && xp && (zero || zero_bytes == 0), "stem_pad_zero: bad arguments");
+    return stem_pad(dtype, x, xp, B, Cin, T, H, W, (hipStream_t)stream, zero, zero_bytes);
+}
+int gdl_bn_act_acc(int dtype, const void* y, const int64_t* acc, const float* gamma, const float* beta, float* running_mean,
+                   float* running_var, int64_t* nbt, float* save_mean, float* save_rstd, float* scale, float* shift,
+                   const void* res, const int64_t* res_acc, const float* res_gamma, const float* res_beta,
+                   float* res_running_mean, float* res_running_var, int64_t* res_nbt, float* res_save_mean, float* res_save_rstd,
+                   float* res_scale, float* res_shift, size_t rows, float eps, float momentum, int relu, void* out,
+                   uint8_t* relu_bits, int C, void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && y && acc && gamma && beta && save_mean && save_rstd && scale && shift && out && rows >= 1,
+                "bn_act_acc: bad arguments");
+    GDL_REQUIRE((res_scale == nullptr) == (res_shift == nullptr) && (res || !res_scale), "bn_act_acc: residual constants without a residual");
+    GDL_REQUIRE(!res_acc || (res_scale && res_gamma && res_beta && res_save_mean && res_save_rstd),
+                "bn_act_acc: residual accumulators need gamma / beta / saved statistics / scale / shift");
+    const BnAccFin fa = acc_consumer_of(acc, C, rows, gamma, beta, running_mean, running_var, nbt, save_mean, save_rstd, scale, shift,
+                                        eps, momentum);
+    const BnAccFin fr = acc_consumer_of(res_acc, C, rows, res_gamma, res_beta, res_running_mean, res_running_var, res_nbt,
+                                        res_save_mean, res_save_rstd, res_scale, res_shift, eps, momentum);
+    return bn_act(dtype, y, scale, shift, res, res_scale, res_shift, relu, out, rows, C, (hipStream_t)stream, relu_bits, &fa,
+                  res_scale ? &fr : nullptr);
+}
+int gdl_bn_relu_maxpool_fwd_acc(int dtype, const void* y, const int64_t* acc, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, int64_t* nbt, float* save_mean, float* save_rstd,
+                                float* scale, float* shift, float eps, float momentum, void* out, uint8_t* idx, void* ymax, int N,
+                                int H, int W, int C, void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && y && acc && gamma && beta && save_mean && save_rstd && scale && shift && out && idx,
+                "bn_relu_maxpool_fwd_acc: bad arguments");
+    const BnAccFin fa = acc_consumer_of(acc, C, (size_t)N * H * W, gamma, beta, running_mean, running_var, nbt, save_mean, save_rstd,
+                                        scale, shift, eps, momentum);
+    return bn_relu_maxpool_fwd(dtype, y, scale, shift, out, idx, ymax, N, H, W, C, (hipStream_t)stream, &fa);
+}
+int gdl_block_bwd_reduce(int dtype, const void* dz, const void* z, const void* y2, const void* yd, const float* mean2,
+                         const float* rstd2, const float* meand, const float* rstdd, void* do2, float* partial2, float* partiald,
+                         size_t M, int C, int premasked, void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && dz && y2 && mean2 && rstd2 && partial2, "block_bwd_reduce: bad arguments");
+    GDL_REQUIRE(!yd || (meand && rstdd && partiald), "block_bwd_reduce: downsample branch without its statistics / partial rows");
+    return block_bwd_reduce(dtype, dz, z, y2, yd, mean2, rstd2, meand, rstdd, do2, partial2, partiald, M, C, (hipStream_t)stream,
+                            premasked != 0);
+}
+int gdl_bn_bwd_apply2(int dtype, const void* g, const void* yA, const float* meanA, const float* rstdA, const float* gammaA,
+                      const float* coefA, void* dyA, const void* yB, const float* meanB, const float* rstdB, const float* gammaB,
+                      const float* coefB, void* dyB, size_t M, int C, void* stream) {
+    GDL_REQUIRE(dt_ok(dtype) && g && yA && meanA && rstdA && gammaA && coefA && dyA && yB && meanB && rstdB && gammaB && coefB && dyB,
+                "bn_bwd_apply2: bad arguments");
+    GDL_REQUIRE(C > 0 && C % (dtype == GDL_BF16 ? 8 : 4) == 0, "bn_bwd_apply2: C=%d unsupported", C);
+    return bn_bwd_apply2(dtype, g, yA, meanA, rstdA, gammaA, coefA, dyA, yB, meanB, rstdB, gammaB, coefB, dyB, M, C,
+                         (hipStream_t)stream);
+}
+int gdl_bn_finalize_train_pair(const float* partialA, int tilesA, double countA, const float* gammaA, const float* betaA,
+                               float* running_meanA, float* running_varA, int64_t* nbtA, float* save_meanA, float* save_rstdA,
+                               float* scaleA, float* shiftA, const float* partialB, int tilesB, double countB, const float* gammaB,
+                               const float* betaB, float* running_meanB, float* running_varB, int64_t* nbtB, float* save_meanB,
+                               float* save_rstdB, float* scaleB, float* shiftB, int C, float eps, float momentum, void* stream) {
+    GDL_REQUIRE(partialA && gammaA && betaA && save_meanA && save_rstdA && scaleA && shiftA && partialB && gammaB && betaB &&
+                    save_meanB && save_rstdB && scaleB && shiftB,
+                "bn_finalize_train_pair: null pointer");
+    const BnFinTrain a{partialA, tilesA, C, countA, gammaA, betaA, running_meanA, running_varA, nbtA, save_meanA, save_rstdA, scaleA, shiftA};
+    const BnFinTrain b{partialB, tilesB, C, countB, gammaB, betaB, running_meanB, running_varB, nbtB, save_meanB, save_rstdB, scaleB, shiftB};
+    return bn_finalize_train_pair(a, b, eps, momentum, (hipStream_t)stream);
+}
+int gdl_bn_bwd_finalize_pair(const float* partialA, int blocksA, double countA, float* dgammaA, float* dbetaA, float* coefA,
+                             const float* partialB, int blocksB, double countB, float* dgammaB, float* dbetaB, float* coefB, int C,
+                             void* stream) {
+    GDL_REQUIRE(partialA && dgammaA && dbetaA && coefA && partialB && dgammaB && dbetaB && coefB, "bn_bwd_finalize_pair: null pointer");
+    const BnFinBwd a{partialA, blocksA, C, countA, dgammaA, dbetaA, coefA}, b{partialB, blocksB, C, countB, dgammaB, dbetaB, coefB};
+    return bn_bwd_finalize_pair(a, b, (hipStream_t)stream);
+}
 int gdl_maxpool_bn_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* scale,
                              const float* shift, const float* save_mean, const float* save_rstd, const float* gamma,
                              const float* coef, void* dy, int N, int H, int W, int C, void* stream) {

@@ -95,6 +95,16 @@ SIGNATURES = {
     "gdl_bn_bwd_finalize": ("i", "pii" + "d" + "ppp" + "p"),
     "gdl_bn_bwd_apply": ("i", "ipppppppp" + "i" + "p" + "zi" + "p"),
     "gdl_relu_bwd": ("i", "ipppzp"),
+    "gdl_bn_acc_scales": ("i", "zpp"),
+    "gdl_conv_fwd_acc": ("i", "ippppp" + "iiiiiiiii" + "pz" + "p"),
+    "gdl_stem_conv_fwd_acc": ("i", "ippppp" + "iiii" + "p"),
+    "gdl_stem_pad_zero": ("i", "ippiiiii" + "pz" + "p"),
+    "gdl_bn_act_acc": ("i", "ip" + "pppppppppp" + "p" + "pppppppppp" + "zff" + "i" + "pp" + "i" + "p"),
+    "gdl_bn_relu_maxpool_fwd_acc": ("i", "ip" + "pppppppppp" + "ff" + "ppp" + "iiii" + "p"),
+    "gdl_block_bwd_reduce": ("i", "ipppp" + "pppp" + "ppp" + "zi" + "i" + "p"),
+    "gdl_bn_bwd_apply2": ("i", "ip" + "pppppp" + "pppppp" + "zi" + "p"),
+    "gdl_bn_finalize_train_pair": ("i", ("pi" + "d" + "pp" + "ppp" + "pppp") * 2 + "i" + "ff" + "p"),
+    "gdl_bn_bwd_finalize_pair": ("i", ("pi" + "d" + "ppp") * 2 + "i" + "p"),
     "gdl_bn_relu_maxpool_fwd": ("i", "ipppppp" + "iiii" + "p"),
     "gdl_maxpool_bn_bwd_apply": ("i", "ippppppppp" + "p" + "iiii" + "p"),
     "gdl_maxpool_bwd": ("i", "ippp" + "iiii" + "p"),

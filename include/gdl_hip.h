@@ -225,6 +225,70 @@ GDL_API int gdl_bn_bwd_apply(int dtype, const void* g, const void* y, const floa
                              int relu_mask, void* dy, size_t M, int C, void* stream);
 /* dx = dy * (out > 0)   (may alias dy) */
 GDL_API int gdl_relu_bwd(int dtype, const void* dy, const void* out, void* dx, size_t n, void* stream);
+/* The fused forms the encoder engine launches by default (GDL_BN_ACC), one entry point per kernel.  They exist so that each
+ * fused kernel can be tested alone (tests/test_bnacc_gpu.py); a training step reaches the same kernels through gdl_encoder_*.
+ *
+ * Forward statistics through integer accumulators.  A convolution's epilogue adds its tiles' per-channel sums, in fixed point,
+ * to `acc`: int64 [C][2] = { round(sum y * s1), round(sum y^2 * s2) } per tile, followed by ONE flag word (int64, index 2 C) --
+ * 2 C + 1 words the caller zeroes before the producer runs.  gdl_bn_acc_scales(rows): the two powers of two for a tensor of
+ * `rows` = N OH OW pixels (host only; s1 = 2^(49 - L), s2 = 2^(36 - L), L = ceil(log2(rows)): exact headroom for |y| < 8192).  A
+ * block whose sum does not fit its share of 2^62 (or is NaN / inf) adds nothing and sets the flag word; the consumer then
+ * publishes NaN statistics.
+ *   gdl_conv_fwd_acc      = gdl_conv_fwd with `acc` [K][2] + flag in place of bn_partial; split_ws / split_ws_bytes optional
+ *                           (NULL: unsplit) as for gdl_conv_fwd_split -- the split-K finish kernel then adds the sums.
+ *   gdl_stem_conv_fwd_acc = gdl_stem_conv_fwd likewise, acc [64][2] + flag.
+ *   gdl_stem_pad_zero     = gdl_stem_pad that also clears `zero_bytes` bytes at `zero` (both multiples of 16: the engine's
+ *                           accumulator arena) in the same launch.
+ *   gdl_bn_act_acc        = gdl_bn_act / gdl_bn_act_bits (relu_bits optional, with relu) whose BatchNorm constants are not
+ *     finalized: every block derives scale / shift of all C <= 512 channels from acc (count = rows, the tensor's M) --
+ *     mean = s / rows, biased variance clamped at 0, rstd, scale = gamma rstd, shift = beta - mean scale, in double -- and block 0
+ *     publishes save_mean, save_rstd, scale, shift (float32 [C], all required), updates running_mean / running_var (unbiased;
+ *     optional) once and adds 1 to *nbt (optional).  Residual: res == NULL none; res alone: the raw tensor; res + res_scale /
+ *     res_shift: res * res_scale + res_shift from those arrays (READ when res_acc == NULL); with res_acc (+ res_gamma, res_beta,
+ *     res_save_mean, res_save_rstd required, the running pair and nbt optional) the residual BatchNorm's constants are derived
+ *     and published the same way, res_scale / res_shift being written.
+ *   gdl_bn_relu_maxpool_fwd_acc = gdl_bn_relu_maxpool_fwd likewise (C <= 256, count = N H W).
+ * Block backward.  gdl_block_bwd_reduce: do2 = dz * (z > 0) with the reductions of bn2 (partial2) and, when yd != NULL, of the
+ * downsample BatchNorm (partiald) in one pass, [gdl_bn_bwd_blocks(M, C)][C][2] = { sum do2, sum do2 * (y - mean) * rstd } each;
+ * premasked != 0: dz already carries the mask, z is not read and do2 not written (both may be NULL).
+ * gdl_bn_bwd_apply2: dyA = gammaA rstdA (g - coefA[0] - xhatA coefA[1]) and dyB likewise from one read of g (no ReLU mask).
+ * gdl_bn_finalize_train_pair / gdl_bn_bwd_finalize_pair: gdl_bn_finalize_train / gdl_bn_bwd_finalize of two BatchNorms of
+ * equal width C in one launch; tile / block counts and counts may differ, the results are those of two single launches. */
+GDL_API int gdl_bn_acc_scales(size_t rows, double* s1, double* s2);
+GDL_API int gdl_conv_fwd_acc(int dtype, const void* x, const void* w_krsc, void* y, int64_t* acc, const void* table, int N, int H,
+                             int W, int C, int K, int R, int S, int stride, int pad, void* split_ws, size_t split_ws_bytes,
+                             void* stream);
+GDL_API int gdl_stem_conv_fwd_acc(int dtype, const void* xp, const void* wp, void* y, int64_t* acc, const void* table, int n_img,
+                                  int H, int W, int Cin, void* stream);
+GDL_API int gdl_stem_pad_zero(int dtype, const float* x, void* xp, int B, int Cin, int T, int H, int W, void* zero,
+                              size_t zero_bytes, void* stream);
+GDL_API int gdl_bn_act_acc(int dtype, const void* y, const int64_t* acc, const float* gamma, const float* beta,
+                           float* running_mean, float* running_var, int64_t* num_batches_tracked, float* save_mean,
+                           float* save_rstd, float* scale, float* shift, const void* res, const int64_t* res_acc,
+                           const float* res_gamma, const float* res_beta, float* res_running_mean, float* res_running_var,
+                           int64_t* res_num_batches_tracked, float* res_save_mean, float* res_save_rstd, float* res_scale,
+                           float* res_shift, size_t rows, float eps, float momentum, int relu, void* out, uint8_t* relu_bits, int C,
+                           void* stream);
+GDL_API int gdl_bn_relu_maxpool_fwd_acc(int dtype, const void* y, const int64_t* acc, const float* gamma, const float* beta,
+                                        float* running_mean, float* running_var, int64_t* num_batches_tracked, float* save_mean,
+                                        float* save_rstd, float* scale, float* shift, float eps, float momentum, void* out,
+                                        uint8_t* idx, void* ymax, int N, int H, int W, int C, void* stream);
+GDL_API int gdl_block_bwd_reduce(int dtype, const void* dz, const void* z, const void* y2, const void* yd, const float* mean2,
+                                 const float* rstd2, const float* meand, const float* rstdd, void* do2, float* partial2,
+                                 float* partiald, size_t M, int C, int premasked, void* stream);
+GDL_API int gdl_bn_bwd_apply2(int dtype, const void* g, const void* yA, const float* meanA, const float* rstdA,
+                              const float* gammaA, const float* coefA, void* dyA, const void* yB, const float* meanB,
+                              const float* rstdB, const float* gammaB, const float* coefB, void* dyB, size_t M, int C,
+                              void* stream);
+GDL_API int gdl_bn_finalize_train_pair(const float* partialA, int tilesA, double countA, const float* gammaA, const float* betaA,
+                                       float* running_meanA, float* running_varA, int64_t* nbtA, float* save_meanA,
+                                       float* save_rstdA, float* scaleA, float* shiftA, const float* partialB, int tilesB,
+                                       double countB, const float* gammaB, const float* betaB, float* running_meanB,
+                                       float* running_varB, int64_t* nbtB, float* save_meanB, float* save_rstdB, float* scaleB,
+                                       float* shiftB, int C, float eps, float momentum, void* stream);
+GDL_API int gdl_bn_bwd_finalize_pair(const float* partialA, int blocksA, double countA, float* dgammaA, float* dbetaA,
+                                     float* coefA, const float* partialB, int blocksB, double countB, float* dgammaB,
+                                     float* dbetaB, float* coefB, int C, void* stream);
 
 /* ------------------------------------------------------------------ pooling
  * nn.MaxPool2d(3,2,1): backbone.py:106, fused with the stem's BN+ReLU:
