@@ -700,6 +700,32 @@ int gdl_frames_resized_crop(const uint8_t* src, size_t src_bytes, const int64_t*
     GDL_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "frames_resized_crop: zero std");
     return frames_resized_crop(src, src_bytes, (const long long*)desc, n_img, T, out_h, out_w, mean, std, out, (hipStream_t)stream);
 }
+int gdl_loader_plan(const int64_t* clips, const int64_t* frames, const int64_t* labels, int64_t N, int T, uint64_t seed, int64_t epoch,
+                    int64_t first, int64_t count, int shuffle, int augment, int64_t n_samples, int64_t start_high, int out_h,
+                    int out_w, const double* draw, int64_t* index, int64_t* label, int64_t* wave_desc, int64_t* crop_desc,
+                    void* stream) {
+    GDL_REQUIRE(clips && frames && labels && draw && index && label && wave_desc && crop_desc, "loader_plan: bad arguments");
+    GDL_REQUIRE((((uintptr_t)clips | (uintptr_t)frames | (uintptr_t)labels | (uintptr_t)index | (uintptr_t)label |
+                  (uintptr_t)wave_desc | (uintptr_t)crop_desc) & 7) == 0, "loader_plan: the tables must be 8-byte aligned");
+    GDL_REQUIRE(N >= 1 && N <= INT32_MAX && T >= 1 && T <= 64, "loader_plan: N (%lld) must be in [1, 2^31 - 1] and T (%d) in [1, 64]",
+                (long long)N, T);
+    GDL_REQUIRE(first >= 0 && count >= 1 && first <= N && count <= N - first,
+                "loader_plan: positions [%lld, %lld + %lld) do not lie inside an epoch of %lld", (long long)first, (long long)first,
+                (long long)count, (long long)N);
+    GDL_REQUIRE((shuffle == 0 || shuffle == 1) && (augment == 0 || augment == 1), "loader_plan: shuffle and augment are 0 or 1");
+    GDL_REQUIRE(n_samples >= 1 && start_high >= 0 && n_samples < INT32_MAX - 4096 && start_high < INT32_MAX - n_samples,
+                "loader_plan: a window of %lld samples starting at up to %lld does not fit 2^31", (long long)n_samples, (long long)start_high);
+    GDL_REQUIRE(out_h > 0 && out_w > 0 && resized_crop_box_ok(1, 1, out_h, out_w),
+                "loader_plan: output size %d x %d does not fit the resize kernel's tables", out_h, out_w);
+    const LoaderDraw dr{draw[0], draw[1], draw[2], draw[3], draw[4], draw[5], draw[6]};
+    GDL_REQUIRE(dr.scale_lo > 0 && dr.scale_lo <= dr.scale_hi && dr.scale_hi < 1e6 && dr.ratio_lo > 0 && dr.ratio_lo <= dr.ratio_hi &&
+                    dr.ratio_hi < 1e6 && dr.log_ratio_lo <= dr.log_ratio_hi && dr.log_ratio_lo > -50 && dr.log_ratio_hi < 50 &&
+                    dr.p_flip >= 0 && dr.p_flip <= 1,
+                "loader_plan: draw = {scale_lo, scale_hi, ratio_lo, ratio_hi, log ratio_lo, log ratio_hi, p_flip} out of range");
+    return loader_plan((const long long*)clips, (const long long*)frames, (const long long*)labels, N, T, seed, epoch, first, count,
+                       shuffle, augment, start_high, dr, (long long*)index, (long long*)label, (long long*)wave_desc,
+                       (long long*)crop_desc, (hipStream_t)stream);
+}
 int gdl_softmax_ce3(const float* logits0, const float* logits1, const float* logits2, const int64_t* labels, float scale0,
                     float scale1, float scale2, float* losses, float* dlogits0, float* dlogits1, float* dlogits2, int B,
                     int n_classes, void* stream) {

@@ -254,6 +254,14 @@ int frames_normalize(const unsigned char* in, size_t n_img, int H, int W, const 
 int resized_crop_box_ok(int box_h, int box_w, int out_h, int out_w);
 int frames_resized_crop(const unsigned char* src, size_t src_bytes, const long long* desc, int n_img, int T, int out_h, int out_w,
                         const float* mean, const float* std, float* out, hipStream_t st);
+// loader.hip: the epoch planner of the device-resident loader (shuffle, window starts, crop boxes and flips as descriptor tables)
+struct LoaderDraw {
+    double scale_lo, scale_hi, ratio_lo, ratio_hi, log_ratio_lo, log_ratio_hi, p_flip;
+};
+int loader_plan(const long long* clips, const long long* frames, const long long* labels, long long N, int T, unsigned long long seed,
+                long long epoch, long long first, long long count, int shuffle, int augment, long long start_high,
+                const LoaderDraw& dr, long long* index, long long* label, long long* wave_desc, long long* crop_desc,
+                hipStream_t st);
 int eval_count(const float* out, const float* out_a, const float* out_v, const int64_t* labels, int B, int n, int64_t* num,
                int64_t* acc, int64_t* acc_a, int64_t* acc_v, hipStream_t st);
 int softmax_ce_multi(int nsets, const float* const* logits, const int64_t* labels, const float* scales, float* losses,

@@ -1,6 +1,9 @@
 // philox.h -- the counter-based normal generator shared by the OGM-GE modulation (optim.hip) and the probabilistic-embedding
 // branch (dul.hip): Philox4x32-10 and Box-Muller.  A value is a function of its counter and key only, never of the launch
-// geometry.  The two users draw from disjoint counter ranges (word 1 of the counter, see dul_noise4).
+// geometry.  The two users draw from disjoint counter ranges (word 1 of the counter, see dul_noise4).  The epoch planner of the
+// device-resident loader (loader.hip) reads the raw words of the same generator with word 1 = 0xC0000000 | purpose << 24 |
+// t << 8 | k: bits 31 and 30 set together, which neither the modulation (word 1 < 2^29) nor the probabilistic-embedding branch
+// (0x80000000 | modality) has, so the three users stay disjoint even under one seed.
 #pragma once
 #include "common.h"
 

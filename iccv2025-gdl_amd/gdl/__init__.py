@@ -16,7 +16,12 @@ def __getattr__(name):
     `gdl.LinearProbe`, `gdl.probe_order`, `gdl.multistep_lr`), and `gdl.ScoreBank`, the evaluation report of gdl.evaluate (mAP,
     top-k, confusion), and the class prototypes of gdl.prototypes (`gdl.Prototypes`, `gdl.prototype_logits`: prototypical modal
     rebalance on the joint step), and `gdl.MLATrainer` with its schedule helper `gdl.mla_alpha` (gdl.mla: alternating unimodal
-    training on a shared head) -- imported on first use (they import torch)."""
+    training on a shared head), and the device-resident epoch loader of gdl.loader (`gdl.DeviceDataset`, `gdl.DeviceLoader`: the
+    shuffle, the window starts, the crop boxes and the flips planned on the device) -- imported on first use (they import torch)."""
+    if name in ("DeviceDataset", "DeviceLoader"):
+        from . import loader
+
+        return getattr(loader, name)
     if name in ("MLATrainer", "mla_alpha"):
         from . import mla
 

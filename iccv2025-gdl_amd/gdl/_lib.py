@@ -17,7 +17,7 @@ ENC_NPARAMS, ENC_NBN = 60, 20
 GDL_JOURNAL_COLS = 16
 
 _C = {"i": ctypes.c_int, "p": ctypes.c_void_p, "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double,
-      "l": ctypes.c_int64, "s": ctypes.c_char_p}
+      "l": ctypes.c_int64, "L": ctypes.c_uint64, "s": ctypes.c_char_p}
 
 # name -> (restype code, argtypes codes); mirrors include/gdl_hip.h one to one
 SIGNATURES = {
@@ -161,6 +161,7 @@ SIGNATURES = {
     "gdl_frames_normalize": ("i", "p" + "lii" + "ppp" + "p"),
     "gdl_frames_resized_crop_box_ok": ("i", "iiii"),
     "gdl_frames_resized_crop": ("i", "pzp" + "iiiii" + "ppp" + "p"),
+    "gdl_loader_plan": ("i", "ppp" + "li" + "Ll" + "ll" + "ii" + "ll" + "ii" + "p" + "pppp" + "p"),
     "gdl_eval_count": ("i", "pppp" + "ii" + "pppp" + "p"),
     "gdl_optim_create": ("i", "pppi"),
     "gdl_optim_destroy": (None, "p"),

@@ -9,6 +9,7 @@ launch each (wave_log_spectrogram / stage_audio, resized_crop_frames / augment_f
 files to PCM samples and uint8 frames, resampling the audio of the 22050 Hz datasets (CREMA-D, AVE; the 16 kHz datasets' files
 are stored at their rate), and drawing the window starts, the crop boxes and the flips -- a few integers per sample
 (random_wave_starts, random_augment_params); everything that touches a sample's or a pixel's value runs on the device.
+gdl.loader (DeviceDataset, DeviceLoader) draws them on the device too, for a dataset that lives there.
 
 Nothing is computed on the CPU: the functions that produce tensors need device tensors and the built library.
 """

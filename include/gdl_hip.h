@@ -563,6 +563,55 @@ GDL_API int gdl_frames_resized_crop_box_ok(int box_h, int box_w, int out_h, int 
 GDL_API int gdl_frames_resized_crop(const uint8_t* src, size_t src_bytes, const int64_t* desc, int n_img, int B, int T, int out_h,
                                     int out_w, const float* mean, const float* std, float* out, void* stream);
 
+/* ------------------------------------------------------------------ the epoch planner of the device-resident loader
+ * What the reference's DataLoader and datasets draw per sample -- the shuffled order (DataLoader(shuffle=True)), the window start
+ * (random.randint, KSDataset.py:139-149), RandomResizedCrop's box and RandomHorizontalFlip's coin per frame
+ * (CramedDataset.py:76-88) -- computed on the device for a whole epoch in ONE launch, as the descriptor tables the two stage
+ * kernels above read.  Nothing is drawn, checked or copied by the host; a value is a function of (seed, epoch, sample index).
+ * gdl_loader_plan fills the tables of `count` consecutive epoch positions first .. first + count - 1.
+ *   In (int64 device memory, 8-byte aligned): clips [N][5] = { byte offset, len, channels, format, limit } -- the first four
+ *   are columns 0..3 of gdl_wave_logspec's rows, limit the tiled length; frames [N][T][3] = { byte offset, H, W }; labels [N].
+ *   Scalars: N in [1, 2^31 - 1], T in [1, 64], seed, epoch, first, count, shuffle and augment (0 / 1), n_samples and start_high
+ *   (the window's length and its largest start: start_high + n_samples < 2^31), out_h x out_w (the resize's output size, which
+ *   must fit that kernel's tables).  draw: seven HOST doubles { scale_lo, scale_hi, ratio_lo, ratio_hi, log(ratio_lo),
+ *   log(ratio_hi), p_flip }; the caller takes the logarithms so that the device and a restatement use the same constants.
+ *   Out (int64 device memory): index [count], label [count], wave_desc [count][6] in gdl_wave_logspec's row format, crop_desc
+ *   [count * T][8] in gdl_frames_resized_crop's row format, frame t of position p at row p * T + t.  Batch k of size B is then
+ *   gdl_wave_logspec(.., wave_desc + 6 B k, B, ..) and gdl_frames_resized_crop(.., crop_desc + 8 B T k, B T, B, T, ..).
+ *   first < 0, count < 1, first + count > N or a limit above: GDL_ERR_ARG, nothing launched, nothing written.
+ * Arithmetic (all integers exact; tests/loader_ref.py restates it on NumPy):
+ *   words(c0, purpose, t, k) = philox4x32_10(counter (c0, 0xC0000000 | purpose << 24 | t << 8 | k, epoch low, epoch high),
+ *   key (seed low, seed high)); purposes PERM 0, BOX 1, FLIP 2, WAVE 3.  Bits 31 and 30 of counter word 1 are set together only
+ *   here (gdl_optim_modulate: word 1 < 2^29; gdl_dul_sample: 0x80000000 | modality), so the three users of one seed stay disjoint.
+ *   u(w) = (w + 0.5) 2^-32.  Every draw is keyed by the sample's index, never by its position: a sample's window, boxes and flips
+ *   in an epoch do not depend on the batch size or the rank layout.
+ *   position -> index: shuffle = 0: the position.  shuffle = 1: a keyed bijection of [0, N) evaluated per element, nothing
+ *   stored or sorted -- a balanced Feistel network on 2 kb bits, kb = max(1, ceil(bit_length(N - 1) / 2)), mask = 2^kb - 1: from
+ *   L = v >> kb, R = v & mask, six rounds (L, R) <- (R, L ^ (words(R, PERM, 0, round)[0] & mask)), v' = L << kb | R; repeated
+ *   from v' while v' >= N (cycle walking; the domain is below 4 N, so fewer than 4 passes on average).  N = 1 gives 0.
+ *   window start = (words(index, WAVE, 0, 0)[0] * (start_high + 1)) >> 32, a 64-bit product; drawn with augment = 0 as well (the
+ *   reference draws it in test mode too).  wave_desc row = { offset, len, channels, format, start, limit }.
+ *   frame t, augment = 1: torchvision's published RandomResizedCrop.get_params in double.  Try k = 0 .. 9, w = words(index, BOX,
+ *   t, k): a = (H W) (scale_lo + (scale_hi - scale_lo) u(w[0])), r = exp(log_ratio_lo + (log_ratio_hi - log_ratio_lo) u(w[1])),
+ *   bw = rint(sqrt(a r)), bh = rint(sqrt(a / r)) (ties to even, Python's round), no operation fused; accepted if 0 < bw <= W and
+ *   0 < bh <= H, then top = (w[2] (H - bh + 1)) >> 32, left = (w[3] (W - bw + 1)) >> 32.  No try accepted: W / H < ratio_lo:
+ *   bw = W, bh = rint(W / ratio_lo); W / H > ratio_hi: bh = H, bw = rint(H ratio_hi); otherwise the whole frame; a side that
+ *   rounds to 0 is 1; top = (H - bh) div 2, left = (W - bw) div 2.  flip = u(words(index, FLIP, t, 0)[0]) < p_flip.
+ *   frame t, augment = 0: the whole frame, no flip (Resize).  A frame with a side outside [1, 65535] gets the whole-frame row in
+ *   either mode; gdl_frames_resized_crop writes such an image as NaN.
+ * Departures from the reference, all in which random stream is read, none in a distribution's shape: Philox instead of Python's
+ *   and torch's Mersenne streams; the range reduction (w n) >> 32 instead of rejection sampling, biased by less than n / 2^32
+ *   (random.randint(0, 80000): 2e-5); a keyed bijection instead of torch.randperm.
+ * The LDS limit of the resize kernel: gdl_frames_resized_crop_box_ok fails only if a side exceeds 65535 or if the tables plus one
+ *   staged row plus one output row's taps exceed 40 KB, and every term of that sum grows with the box's sides (tap counts, the
+ *   staged row, the taps' rows); so if the whole frame passes, every box inside it passes.  The planner therefore does not test
+ *   boxes: the owner of the dataset tests each distinct frame size once (gdl.DeviceDataset does), and the stage kernel's own
+ *   guard (NaN) stays as the backstop. */
+GDL_API int gdl_loader_plan(const int64_t* clips, const int64_t* frames, const int64_t* labels, int64_t N, int T, uint64_t seed,
+                            int64_t epoch, int64_t first, int64_t count, int shuffle, int augment, int64_t n_samples,
+                            int64_t start_high, int out_h, int out_w, const double* draw, int64_t* index, int64_t* label,
+                            int64_t* wave_desc, int64_t* crop_desc, void* stream);
+
 /* ------------------------------------------------------------------ clip + grad stats + SGD
  * clip_grad_norm_(params, 40, 2) (main_dgl.py:129), the logged
  * sum_p mean|grad_p| per encoder (:132-143) and optim.SGD(momentum, weight_decay)
