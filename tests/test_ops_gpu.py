@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_ref as cr
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +117,11 @@ def test_conv_dgrad(shape, dt, with_addend):
     torch.cuda.synchronize()
     got = from_nhwc(dx)
     assert relerr(got, ref) < tol(dt, 2e-6, 4e-3), relerr(got, ref)
+    # and element by element against float64 (tests/conv_ref.py; a launch with an addend rounds twice: r = 2)
+    ref64, mag = (cr.conv_dgrad_s1 if stride == 1 else cr.conv_dgrad_s2)(dy, w, (H, W), pad)
+    extras = [add.astype(np.float64)] if with_addend else []
+    ref64 = ref64 + sum(extras)
+    cr.check(got, ref64, cr.bound(ref64, mag, R * R * K, tol(dt, 0.0, cr.U_BF16), 2 if with_addend else 1, extras))
 
 
 @pytest.mark.parametrize("shape", [
@@ -208,6 +214,12 @@ def test_conv_dgrad_ds(shape, dt, with_bits):
     torch.cuda.synchronize()
     got = from_nhwc(dx)
     assert relerr(got, ref) < tol(dt, 2e-6, 4e-3), relerr(got, ref)
+    # and element by element against float64 (tests/conv_ref.py): 9 K + K products per element, exact zeros under cleared bits
+    ref64, mag = cr.conv_dgrad_ds(dy, w, dyd, wds, (H, W))
+    zero = ~(z > 0) if with_bits else None
+    if with_bits:
+        ref64 = np.where(zero, 0.0, ref64)
+    cr.check(got, ref64, cr.bound(ref64, mag, 10 * K, tol(dt, 0.0, cr.U_BF16)), zero_where=zero)
 
 
 WGRAD_SHAPES = [
